@@ -1,6 +1,6 @@
 """Benchmark: PPO actor-learner SPS + PPO updates/sec, ALE/Pong-v5 obj-mode (synthetic env), PPO_OBJ.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,10 +10,13 @@ rank: a T=128-step rollout of local_num_envs=128 envs (BASELINE config 2 per GPU
 RCCL gradient all-reduce per minibatch when N > 1 (ppo_atari_multigpu semantics, weak scaling).
 value = env steps of all ranks / max-over-ranks wall time of the K timed iterations.
 
-Rank 0 prints ONE JSON line. Extra fields: `roofline` (dominant HIP kernel of this package, live
-HIP-event timing over the timed region), `kernels` (every HIP kernel's mean launch duration and
-algorithmic GB/s), `roofline_scaled` (N=1: the north-star kernels the timed path runs -- GAE, minibatch
-prepare, the fused heads + loss pair -- and the rollout head and ReLU backward re-timed cold at
+Rank 0 prints ONE JSON line. A plain run sets up, warms up, times the K steps, writes the last
+step's outputs if --dump-outputs is given (dump_outputs), and prints the line; everything else the
+bench measures or checks runs only with --full, after the timed region, and is null in a plain
+line. Extra fields with --full: `replicas` (the parameter checksums; also whenever N > 1),
+`roofline` (dominant HIP kernel of this package, live HIP-event timing over the timed region),
+`kernels` (every HIP kernel's mean launch duration and algorithmic GB/s), `roofline_scaled`
+(N=1: the north-star kernels the timed path runs -- GAE, minibatch prepare, the fused heads + loss pair -- and the rollout head and ReLU backward re-timed cold at
 streaming sizes, where HBM rather than launch latency bounds them; same algorithmic-byte formulas,
 tools/kernel_bench.py cases), `cpu_baseline` (the oracle's CPU port of
 the same loop timed on this host, N=1).
@@ -27,6 +30,7 @@ import sys
 import time
 from pathlib import Path
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -227,6 +231,64 @@ def relu_bias_wgrad_bytes(name: str):
     return R * N * 8 + R * K * 4 + N * (K + 1) * 4
 
 
+DUMP_ARRAY_ELEMS = 4 << 20  # a larger array is dumped as a fixed, seeded sample of this many
+DUMP_LIMIT_BYTES = 64 << 20  # the whole dump
+
+
+def dump_outputs(directory, arrays: dict) -> dict:
+    """--dump-outputs DIR: what the timed path computed in its last step, one DIR/<name>.npy per
+    array, float64 where the path computes in float64 and float32 otherwise (integer actions and
+    bf16 / u8 observations are exact in float32). An array of more than DUMP_ARRAY_ELEMS elements
+    is written as its elements at sorted indices drawn once from numpy's RandomState(0): the same
+    indices in every run and every build, so two dumps compare element for element. Returns
+    {name: shape written} for the result line."""
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    written, total = {}, 0
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach()
+        if t.numel() > DUMP_ARRAY_ELEMS:
+            idx = np.sort(np.random.RandomState(0).randint(0, t.numel(), DUMP_ARRAY_ELEMS))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_LIMIT_BYTES:
+            raise SystemExit(f"--dump-outputs: more than {DUMP_LIMIT_BYTES} bytes at {name!r}")
+        np.save(out / f"{name}.npy", a)
+        written[name] = list(a.shape)
+    return written
+
+
+METRIC_KEYS = ("charts/learning_rate", "losses/value_loss", "losses/policy_loss", "losses/entropy",
+               "losses/old_approx_kl", "losses/approx_kl", "losses/clipfrac",
+               "losses/explained_variance", "losses/loss")
+
+
+def ppo_outputs(tr) -> dict:
+    """The last iteration as a caller of PPOTrainer.train_iteration holds it: its metric scalars
+    (METRIC_KEYS order), the updated parameters (flat, in optimizer order), the per-minibatch loss
+    statistics, and the rollout it collected (observations, actions, log-probs, rewards, dones,
+    values) with the GAE advantages and returns."""
+    m = tr.last_metrics
+    return {"metrics": torch.tensor([m.get(k, float("nan")) for k in METRIC_KEYS],
+                                    dtype=torch.float64),
+            "params": torch.cat([p.detach().reshape(-1) for p in tr.params]),
+            "loss_stats": tr.stats, "obs": tr.obs, "actions": tr.actions,
+            "logprobs": tr.logprobs, "rewards": tr.rewards, "dones": tr.dones,
+            "values": tr.values, "advantages": tr.advantages, "returns": tr.returns}
+
+
+def dqn_outputs(tr, m: dict) -> dict:
+    """The last global steps as a caller of DQNTrainer.steps holds them: the Q-network and target
+    parameters, the TD statistics, the last sampled batch with its Q gradient, and the env's
+    current observation."""
+    return {"metrics": torch.tensor([m["losses/td_loss"], m["losses/q_values"],
+                                     m["charts/epsilon"]], dtype=torch.float64),
+            "q_params": torch.cat([p.detach().reshape(-1) for p in tr.q.parameters()]),
+            "target_params": tr.t_flat, "dq": tr.dq, "net_obs": tr.net_obs,
+            **{f"batch_{k}": v for k, v in tr.batch.items()}}
+
+
 def free_port() -> int:
     import socket
 
@@ -291,7 +353,18 @@ def launch(argv, gpus: int, script=None, deadline_s: float | None = None) -> int
     try:
         rc = p.wait(timeout=deadline_s)
     except subprocess.TimeoutExpired:
-        os.killpg(p.pid, signal.SIGKILL)
+        # SIGTERM first: torch.distributed.run starts every rank in a session of its own and
+        # ends them itself when it is told to stop; a SIGKILL of its group alone leaves the
+        # ranks running
+        os.killpg(p.pid, signal.SIGTERM)
+        try:
+            p.wait(timeout=10)
+        except subprocess.TimeoutExpired:
+            pass
+        try:
+            os.killpg(p.pid, signal.SIGKILL)
+        except ProcessLookupError:
+            pass
         p.wait()
         ranks = read_status(status)
         rec = {"metric": None, "value": None, "n_gpus": gpus, "error": "launcher deadline",
@@ -351,6 +424,13 @@ def main():
                          "dqn_atari_oc.py SpaceInvaders obj, 1M-row HBM replay (a step = 1000 "
                          "global steps)")
     ap.add_argument("--envs-per-gpu", type=int, default=None)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy "
+                         "(rank 0; dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run everything beside the headline figure: "
+                         "the per-kernel timer and rooflines, the scaled rooflines, the CPU "
+                         "baseline legs, the replica checksums (each still has its --no-* switch)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-iterations", type=int, default=3)
     ap.add_argument("--no-cpu-blocks", action="store_true",
@@ -382,6 +462,8 @@ def main():
                     help="CPU rehearsal of the fail-fast path (gloo, no GPU): the ranks run "
                          "all-reduce iterations and RANK stops before its second one")
     opt = ap.parse_args()
+    if not opt.full:
+        opt.no_cpu_baseline = opt.no_kernel_timing = opt.no_scaled = True
     if needs_launch(opt.gpus):
         # nothing has touched the GPU yet in this process
         raise SystemExit(launch(sys.argv[1:], opt.gpus, deadline_s=opt.deadline + 30))
@@ -519,6 +601,7 @@ def run_dqn(opt, rank: int, world: int, line_out, watch):
     dt = time.perf_counter() - t0
     m = tr.metrics()
     watch.phase("report", stall_s=max(opt.deadline, 600.0))
+    dumped = dump_outputs(opt.dump_outputs, dqn_outputs(tr, m)) if opt.dump_outputs else None
     roofline = dqn_roofline(tr) if not opt.no_kernel_timing else None
     cpu = None
     if not opt.no_cpu_baseline:
@@ -549,6 +632,8 @@ def run_dqn(opt, rank: int, world: int, line_out, watch):
         "updates_per_sec": round(steps / args.train_frequency / dt, 2),
         "us_per_global_step": round(dt / steps * 1e6, 3),
         "td_loss": m["losses/td_loss"],
+        "full": opt.full,
+        "dumped": dumped,
         "roofline": roofline,
         "cpu_baseline": cpu,
     }
@@ -643,9 +728,15 @@ def run_rank(opt, rank: int, world: int, line_out, watch):
         t = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
-    watch.phase("replica check")
-    replicas = replica_check(tr, world, device)
-    # after the timed region, the kernel timer's replays, the scaled cases and the CPU legs
+    dumped = None
+    if opt.dump_outputs and rank == 0:
+        watch.phase("dump outputs", stall_s=300.0)
+        dumped = dump_outputs(opt.dump_outputs, ppo_outputs(tr))
+    replicas = None
+    if opt.full or world > 1:  # the DP invariant is checked in every multi-rank run
+        watch.phase("replica check")
+        replicas = replica_check(tr, world, device)
+    # after the timed region, the kernel timer's replays, the scaled cases and the CPU legs (--full)
     watch.phase("report", stall_s=max(opt.deadline, 600.0))
 
     env_steps = opt.steps * args.num_steps * args.local_num_envs * world
@@ -851,6 +942,8 @@ def run_rank(opt, rank: int, world: int, line_out, watch):
                            "dp_overlap": bool(args.dp_overlap)} if tr.dp else {})},
             "replicas": replicas,
             "updates_per_sec": round(updates / dt, 2),
+            "full": opt.full,
+            "dumped": dumped,
             "roofline": roofline,
             "roofline_hbm": roofline_hbm if roofline_hbm is not roofline else None,
             "rooflines_top": recs[:6],

@@ -24,6 +24,7 @@ Fixtures:
                       before, after the first and after the second update, and both grad norms
   init_{name}.json    per-parameter checksums of seeded default-size agents + outputs on a fixed
                       input (pins layer order, state-dict keys and orthogonal init order)
+  args_fields.json    the field names of ppo_atari_oc.py's Args dataclass
 
     python tests/golden/gen_golden.py [update_config2 update_config3 ...]
 """
@@ -737,6 +738,17 @@ def gen_replay(size=7, obs_shape=(4, 5), adds=10, seed=31, name="replay_sb3"):
     np.savez_compressed(OUT / f"{name}.npz", **out)
 
 
+def gen_args_fields():
+    """args_fields.json: the names of the reference script's Args fields, in declaration order
+    (tests/test_args_cpu.py checks that this package's Args has every one)."""
+    import ast
+
+    cls = next(n for n in ast.parse(SCRIPT.read_text()).body
+               if isinstance(n, ast.ClassDef) and n.name == "Args")
+    names = [s.target.id for s in cls.body if isinstance(s, ast.AnnAssign)]
+    (OUT / "args_fields.json").write_text(json.dumps(names, indent=1) + "\n")
+
+
 def main():
     torch.set_num_threads(8)
     if sys.argv[1:]:  # just the named fixtures, e.g. update_config2 update_config3
@@ -773,6 +785,7 @@ def main():
     gen_update_config2()
     # config 3's NatureCNN at a real minibatch size (2048), rollout-structured pixel stacks
     gen_update_config3()
+    gen_args_fields()
     print("fixtures written to", OUT)
 
 

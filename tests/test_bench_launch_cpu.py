@@ -194,3 +194,27 @@ def test_kernel_site_byte_counts():
     assert bench.relu_bias_grad_bytes(f"relu_bias_grad_{R}x{N}_norelu") == R * N * 4 + 4 * N
     assert bench.relu_bias_grad_bytes(f"relu_bias_grad_bits_{R}x{N}") == \
         R * N * 8 + R * N // 8 + 4 * N
+
+
+def test_dump_outputs_dtypes_sample_and_limit(tmp_path, monkeypatch):
+    """--dump-outputs: float64 stays float64, everything else is written exactly as float32; an
+    array above the element cap is the same seeded sample in every call; the byte limit holds."""
+    import numpy as np
+
+    monkeypatch.setattr(bench, "DUMP_ARRAY_ELEMS", 1000)
+    big = torch.arange(5000, dtype=torch.int64).reshape(50, 100)
+    arrays = {"f64": torch.linspace(0, 1, 7, dtype=torch.float64),
+              "bf16": torch.tensor([1.5, -2.25], dtype=torch.bfloat16), "big": big}
+    shapes = bench.dump_outputs(tmp_path / "a", arrays)
+    bench.dump_outputs(tmp_path / "b", arrays)
+    assert shapes == {"f64": [7], "bf16": [2], "big": [1000]}
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in arrays}
+    assert a["f64"].dtype == np.float64 and np.array_equal(a["f64"], arrays["f64"].numpy())
+    assert a["bf16"].dtype == np.float32 and a["bf16"].tolist() == [1.5, -2.25]
+    assert a["big"].dtype == np.float32 and np.all(np.diff(a["big"]) >= 0)
+    assert np.array_equal(a["big"], np.load(tmp_path / "b" / "big.npy"))
+    idx = np.sort(np.random.RandomState(0).randint(0, 5000, 1000))
+    assert np.array_equal(a["big"], idx.astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4000)
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(tmp_path / "c", arrays)

@@ -3,7 +3,7 @@ ranks share cuda:0 and exchange gradients over gloo (RCCL needs distinct devices
 the RCCL path at 2/4/8 GPUs). Checks: graphs per minibatch + all-reduce between replays work,
 replicas stay bit-identical, and rank-dependent rollouts really differ."""
 import os
-import socket
+import tempfile
 
 import pytest
 import torch
@@ -11,12 +11,6 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 pytestmark = pytest.mark.gpu
-
-
-def _port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
 
 
 # Config 2 per rank (ppo_atari_oc.py Pong obj, PPObj at the reference's default encoder (256, 512,
@@ -54,9 +48,14 @@ class GlooStandIn:
             dist.all_reduce(t, op=dist.ReduceOp.SUM)
 
 
-def _worker(rank, world, port, out, fused_opt, graphs, overlap=True, dims=None, standin=False):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+def _rendezvous():
+    """A file rendezvous for the ranks of one spawn: a TCP port found free here could be taken by
+    any other process on the host before rank 0 listens on it, seconds later."""
+    return "file://" + os.path.join(tempfile.mkdtemp(prefix="ocppo_dp_"), "store")
+
+
+def _worker(rank, world, store, out, fused_opt, graphs, overlap=True, dims=None, standin=False):
+    dist.init_process_group("gloo", init_method=store, rank=rank, world_size=world)
     from oc_cleanrl_amd.trainer import PPOTrainer
 
     args = _dp_args(world, dims or TOY2, fused_optimizer=fused_opt, cuda_graphs=graphs,
@@ -84,8 +83,7 @@ def _worker(rank, world, port, out, fused_opt, graphs, overlap=True, dims=None, 
 def test_two_ranks_share_one_gpu_over_gloo(fused_opt, graphs):
     mgr = mp.Manager()
     out = mgr.dict()
-    port = _port()
-    mp.spawn(_worker, args=(2, port, out, fused_opt, graphs), nprocs=2, join=True)
+    mp.spawn(_worker, args=(2, _rendezvous(), out, fused_opt, graphs), nprocs=2, join=True)
     (p0, a0), (p1, a1) = out[0], out[1]
     assert torch.equal(p0, p1), "DP replicas diverged"
     assert not torch.equal(a0, a1), "ranks must roll out different env shards"
@@ -100,20 +98,19 @@ def test_overlapped_exchange_equals_the_whole_buffer_exchange():
     for overlap in (True, False):
         mgr = mp.Manager()
         out = mgr.dict()
-        mp.spawn(_worker, args=(2, _port(), out, True, True, overlap), nprocs=2, join=True)
+        mp.spawn(_worker, args=(2, _rendezvous(), out, True, True, overlap), nprocs=2, join=True)
         res.append(out[0][0])
     assert torch.equal(res[0], res[1])
 
 
 
-def _rccl_worker(rank, world, port, out, overlap, graphs, mode="rccl", dims=None, box=True):
+def _rccl_worker(rank, world, store, out, overlap, graphs, mode="rccl", dims=None, box=True):
     """The RCCL exchange path at world size 1: nccl (= RCCL) process group bound to cuda:0,
     against the plain single-GPU trainer in the same process. mode "rccl": the package's own
     communicator, each epoch's all-reduces captured in its graph (the tail's on a side stream
     during the lower backward); "torch": torch.distributed collectives between per-minibatch
     graphs (async tail all-reduce overlapped with the g_low replay, the head, g_opt);
     "torch-graph": torch's collectives captured with the epoch."""
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     from oc_cleanrl_amd import frames
@@ -133,7 +130,7 @@ def _rccl_worker(rank, world, port, out, overlap, graphs, mode="rccl", dims=None
         plain.train_iteration()
     torch.cuda.synchronize()
     assert not plain.dp
-    dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
+    dist.init_process_group("nccl", init_method=store, rank=rank, world_size=world, device_id=dev)
     assert dist.get_backend() == "nccl"
     tr = PPOTrainer(args(True), dev)
     assert tr.dp and bool(tr.split) == overlap
@@ -165,7 +162,7 @@ def test_rccl_exchange_one_rank_matches_single_gpu(overlap, graphs, mode):
     torch's collectives between per-minibatch graphs, and through torch's collectives captured."""
     mgr = mp.Manager()
     out = mgr.dict()
-    mp.spawn(_rccl_worker, args=(1, _port(), out, overlap, graphs, mode), nprocs=1,
+    mp.spawn(_rccl_worker, args=(1, _rendezvous(), out, overlap, graphs, mode), nprocs=1,
              join=True)
     assert out["same_actions"]
     assert torch.equal(out["plain"], out["dp"]), \
@@ -180,7 +177,7 @@ def test_overlapped_exchange_equals_single_allreduce(graphs):
     for overlap in (False, True):
         mgr = mp.Manager()
         out = mgr.dict()
-        mp.spawn(_worker, args=(2, _port(), out, True, graphs, overlap), nprocs=2, join=True)
+        mp.spawn(_worker, args=(2, _rendezvous(), out, True, graphs, overlap), nprocs=2, join=True)
         res.append(out[0][0])
     assert torch.equal(res[0], res[1])
 
@@ -195,7 +192,7 @@ def test_dp_exchange_one_rank_matches_single_gpu_at_config2(overlap, graphs, mod
     the split chain runs the same products in the same order as the uncut one."""
     mgr = mp.Manager()
     out = mgr.dict()
-    mp.spawn(_rccl_worker, args=(1, _port(), out, overlap, graphs, mode, CONFIG2), nprocs=1,
+    mp.spawn(_rccl_worker, args=(1, _rendezvous(), out, overlap, graphs, mode, CONFIG2), nprocs=1,
              join=True)
     assert out["same_actions"]
     assert torch.equal(out["plain"], out["dp"]), \
@@ -215,7 +212,8 @@ def test_overlapped_exchange_equals_whole_at_config2(standin):
     for overlap in (False, True):
         mgr = mp.Manager()
         out = mgr.dict()
-        mp.spawn(_worker, args=(2, _port(), out, True, not standin, overlap, CONFIG2, standin),
+        mp.spawn(_worker,
+                 args=(2, _rendezvous(), out, True, not standin, overlap, CONFIG2, standin),
                  nprocs=2, join=True)
         (p0, a0), (p1, a1) = out[0], out[1]
         assert torch.equal(p0, p1), "DP replicas diverged"
@@ -231,6 +229,6 @@ def test_config2_cut_without_the_box_is_not_the_plain_chain():
     chain's after 3 iterations (round 5's checksums 0c39... vs 0ebad...)."""
     mgr = mp.Manager()
     out = mgr.dict()
-    mp.spawn(_rccl_worker, args=(1, _port(), out, True, True, "rccl", CONFIG2, False), nprocs=1,
-             join=True)
+    mp.spawn(_rccl_worker, args=(1, _rendezvous(), out, True, True, "rccl", CONFIG2, False),
+             nprocs=1, join=True)
     assert not torch.equal(out["plain"], out["dp"])

@@ -17,7 +17,7 @@ else
     > "$OUT/gpu_tests.log" 2>&1
 fi
 tail -3 "$OUT/gpu_tests.log"
-timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-scaled > "$OUT/bench_line.json" 2> "$OUT/bench_line.err"
+timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-scaled > "$OUT/bench_line.json" 2> "$OUT/bench_line.err"
 head -c 400 "$OUT/bench_line.json"; echo
 timeout -k 10 300 python3 bench.py --gpus 2 --backend gloo --device-index 0 --steps 5 --warmup 2 \
   --no-kernel-timing > "$OUT/bench_gpus2.json" 2> "$OUT/bench_gpus2.err"

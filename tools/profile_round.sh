@@ -12,7 +12,7 @@ REPO="$GRAFT_REPO_ROOT"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench" -o bench \
-  -- python3 "$REPO/bench.py" --steps 10 --warmup 3 --no-cpu-baseline --no-scaled \
+  -- python3 "$REPO/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline --no-scaled \
   > "$OUT/bench.log" 2>&1
 echo "bench trace done"
 for case in "gae config" "gae scaled" "heads_loss config" "heads_loss scaled" \

@@ -13,11 +13,11 @@ cd "$R"
 timeout -k 10 600 python3 -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread \
   > "$OUT/gpu_tests.log" 2>&1
 tail -2 "$OUT/gpu_tests.log"
-timeout -k 10 400 python3 bench.py > "$OUT/bench_line.json" 2> "$OUT/bench_line.err"
+timeout -k 10 400 python3 bench.py --full > "$OUT/bench_line.json" 2> "$OUT/bench_line.err"
 head -c 300 "$OUT/bench_line.json"; echo
-timeout -k 10 300 python3 bench.py --config 1 > "$OUT/bench_line_config1.json" 2> "$OUT/bench_line_config1.err"
+timeout -k 10 300 python3 bench.py --full --config 1 > "$OUT/bench_line_config1.json" 2> "$OUT/bench_line_config1.err"
 head -c 200 "$OUT/bench_line_config1.json"; echo
-timeout -k 10 400 python3 bench.py --config 3 --no-cpu-baseline > "$OUT/bench_line_config3.json" \
+timeout -k 10 400 python3 bench.py --full --config 3 --no-cpu-baseline > "$OUT/bench_line_config3.json" \
   2> "$OUT/bench_line_config3.err"
 head -c 200 "$OUT/bench_line_config3.json"; echo
 timeout -k 10 300 python3 bench.py --gpus 2 --backend gloo --device-index 0 --steps 5 --warmup 2 \
