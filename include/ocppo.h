@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCPPO_ABI_VERSION 28
+#define OCPPO_ABI_VERSION 29
 
 /* status codes */
 #define OCPPO_OK 0
@@ -820,6 +820,45 @@ OCPPO_API int ocppo_td_loss_fwd_bwd(ocppo_stream_t stream, const float* q, const
                                     const int64_t* actions, const float* rewards,
                                     const float* dones, int64_t B, int64_t A, double gamma,
                                     float* dq, float* stats);
+
+/* ---------------------------------------------------------------------------------------------
+ * C51 (cleanrl/c51_atari_oc.py, QNetwork_C51 of architectures/dqn.py:36-72). The network emits
+ * [rows, A * N] logits, N atoms per action; `atoms` [N] f32 is the module's registered buffer
+ * (torch.linspace(v_min, v_max, N): its spacing atoms[1] - atoms[0] is read from the buffer, for
+ * linspace(-10, 10, 51) that is 0.39999962, not 0.4). 2 <= N <= 128, 1 <= A <= 18.
+ *
+ * ocppo_c51_loss_fwd_bwd: the train step's loss block :339-359 and its backward w.r.t. the online
+ * logits as ONE launch (one workgroup, no float atomics, no workspace, bitwise repeatable,
+ * graph-replay safe: every output is fully rewritten).
+ *   logits      : [B, A * N] q_network on observations;  logits_next : target_network on
+ *                 next_observations;  actions : [B] i64;  rewards, dones : [B] f32
+ *   next action = first argmax_a sum_k softmax(logits_next[b, a])_k * atoms_k, p' its pmf
+ *   next_atoms  = r + (f32(gamma) * atoms) * (1 - d); tz = clamp(next_atoms, v_min, v_max);
+ *                 b = (tz - v_min) / delta_z; l = floor(b), u = ceil(b) clamped to [0, N - 1];
+ *                 target[l] += (u + (l == u) - b) * p' for every source atom in ascending order,
+ *                 then target[u] += (b - l) * p' likewise (index_add_'s CPU order)
+ *   p = softmax(logits[b, a_b]);  loss = mean_b(-sum_k target_k * log(clamp(p_k, 1e-5, 1 - 1e-5)))
+ *   dlogits     : [B, A * N] = d loss / d logits (through the clamp: zero where p is outside
+ *                 [1e-5, 1 - 1e-5]; through the softmax; scaled by 1 / B); rows of the actions
+ *                 not taken are written as zeros
+ *   stats       : [2] = {losses/loss, losses/q_values = mean_b sum_k p_k * atoms_k}
+ *   target_pmfs : [B, N] or NULL;  next_action : [B] i64 or NULL
+ *
+ * ocppo_c51_epsilon_greedy: q[e, a] = sum_k softmax(logits[e, a])_k * atoms_k (get_action) and
+ * ocppo_epsilon_greedy's choice on it in one launch (same coin, random action and first-maximum
+ * rule; same arguments).  q_out : [E, A] or NULL.
+ * ------------------------------------------------------------------------------------------- */
+OCPPO_API int ocppo_c51_loss_fwd_bwd(ocppo_stream_t stream, const float* logits,
+                                     const float* logits_next, const float* atoms,
+                                     const int64_t* actions, const float* rewards,
+                                     const float* dones, int64_t B, int64_t A, int64_t N,
+                                     double gamma, double v_min, double v_max, float* dlogits,
+                                     float* stats, float* target_pmfs, int64_t* next_action);
+OCPPO_API int ocppo_c51_epsilon_greedy(ocppo_stream_t stream, const float* logits,
+                                       const float* atoms, int64_t E, int64_t A, int64_t N,
+                                       uint64_t seed, const int64_t* step, int64_t step_offset,
+                                       double start_e, double end_e, double duration,
+                                       int64_t* actions, float* epsilon_out, float* q_out);
 
 /* ---------------------------------------------------------------------------------------------
  * Synthetic device-resident env (benchmark / test harness; ALE and OCAtari are not available).

@@ -201,10 +201,10 @@ class DQNTrainer:
         self.pixels = self.env.pixels
         self.A = self.env.n_actions
         self.obs_shape = self.env.single_obs_shape
-        self.q = make_qnet(a, self.obs_shape, self.A).to(self.dev)
-        self.target = make_qnet(a, self.obs_shape, self.A).to(self.dev)
+        self.q = self._make_net().to(self.dev)
+        self.target = self._make_net().to(self.dev)
         self.target.load_state_dict(self.q.state_dict())  # :315
-        self.opt = ops.FlatAdam(self.q.parameters(), lr=a.learning_rate, eps=1e-8)
+        self.opt = ops.FlatAdam(self.q.parameters(), lr=a.learning_rate, eps=self._adam_eps())
         # the target net's parameters as views of one flat buffer too (soft update = 2 ops)
         t_params = [p for p in self.target.parameters()]
         offs, n = ops.flat_offsets(t_params)
@@ -260,6 +260,20 @@ class DQNTrainer:
         frame = self.env.reset()
         ops.obs_reset(frame, self.stacks[0], self.net_obs)
 
+    # ---- what a learner on the same loop replaces (c51.C51Trainer) ------------------------------
+    def _make_net(self) -> nn.Module:
+        return make_qnet(self.args, self.obs_shape, self.A)
+
+    def _adam_eps(self) -> float:
+        return 1e-8  # optim.Adam's default
+
+    def _act(self, k: int):
+        """Greedy / random actions of global step chunk base + k + 1 from the whole network."""
+        a = self.args
+        q = _q_forward(self.q, self.net_obs)
+        ops.epsilon_greedy(q, a.seed, self.step_dev, a.start_e, a.end_e, self.duration,
+                           self.actions, self.epsilon, step_offset=k + 1)
+
     # ------------------------------------------------------------------------------------------
     def _env_step(self, k: int, advance: int = 0) -> bool:
         """One global step (:345-372): act, step, store + VecNormalize, replay add. With the
@@ -286,9 +300,7 @@ class DQNTrainer:
                                           a.start_e, a.end_e, self.duration, self.actions,
                                           self.epsilon, step_offset=k + 1)
             else:
-                q = _q_forward(self.q, self.net_obs)
-                ops.epsilon_greedy(q, a.seed, self.step_dev, a.start_e, a.end_e, self.duration,
-                                   self.actions, self.epsilon, step_offset=k + 1)
+                self._act(k)
         self.env.step(self.actions, k)
         if a.vecnorm_reward:
             # VecNormalize(envs, norm_obs=False, norm_reward=True) (:298) keeps SB3's default

@@ -2445,3 +2445,67 @@ def td_loss_fwd_bwd(q, q_next, actions, rewards, dones, gamma: float, dq=None, s
          _check(rewards, "rewards", f, dev, B), _check(dones, "dones", f, dev, B), B, A,
          float(gamma), _check(dq, "dq", f, dev, B * A), _check(stats, "stats", f, dev, 2))
     return stats, dq
+
+
+# ---------------------------------------------------------------------------------------------
+# C51 (c51_atari_oc.py): expected-value epsilon-greedy, fused projection + cross-entropy loss
+# ---------------------------------------------------------------------------------------------
+C51_MAX_ATOMS, C51_MAX_ACTIONS = 128, 18
+
+
+def _c51_shape(logits, atoms, name: str):
+    """(rows, A, N) of [rows, A * N] logits against the [N] atoms buffer."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2:
+        raise ValueError(f"{name}: expected [rows, A * N] logits")
+    if not isinstance(atoms, torch.Tensor) or atoms.dim() != 1:
+        raise ValueError("atoms: expected the [N] atoms buffer")
+    rows, AN = logits.shape
+    N = atoms.shape[0]
+    if not 2 <= N <= C51_MAX_ATOMS:
+        raise ValueError(f"atoms: N={N}, need 2 <= N <= {C51_MAX_ATOMS}")
+    if rows < 1 or AN % N or not 1 <= AN // N <= C51_MAX_ACTIONS:
+        raise ValueError(f"{name}: shape {tuple(logits.shape)} is not [rows >= 1, A * {N}] with "
+                         f"1 <= A <= {C51_MAX_ACTIONS}")
+    return rows, AN // N, N
+
+
+def c51_epsilon_greedy(logits, atoms, seed: int, step, start_e: float, end_e: float,
+                       duration: float, actions_out=None, epsilon_out=None, step_offset: int = 0,
+                       q_out=None):
+    """epsilon_greedy((softmax(logits.view(E, A, N), 2) * atoms).sum(2), ...) in one launch
+    (QNetwork_C51.get_action's expected Q + c51_atari_oc.py:303-308)."""
+    E, A, N = _c51_shape(logits, atoms, "logits")
+    dev = logits.device
+    f = torch.float32
+    if actions_out is None:
+        actions_out = torch.empty(E, dtype=torch.int64, device=dev)
+    call("ocppo_c51_epsilon_greedy", _stream(dev), _check(logits, "logits", f, dev),
+         _check(atoms, "atoms", f, dev), E, A, N, int(seed) & 0xFFFFFFFFFFFFFFFF,
+         _check(step, "step", torch.int64, dev, 1), int(step_offset), float(start_e),
+         float(end_e), float(duration), _check(actions_out, "actions", torch.int64, dev, E),
+         _opt(epsilon_out, "epsilon_out", f, dev, 1), _opt(q_out, "q_out", f, dev, E * A))
+    return actions_out
+
+
+def c51_loss_fwd_bwd(logits, logits_next, atoms, actions, rewards, dones, gamma: float,
+                     v_min: float, v_max: float, dlogits=None, stats=None, target_pmfs=None,
+                     next_action=None):
+    """c51_atari_oc.py:339-359 and its backward in one launch: (stats [2] = {loss, mean expected
+    Q of the taken actions}, dlogits [B, A * N] = d loss / d logits). target_pmfs [B, N] f32 and
+    next_action [B] i64, when given, receive the projected target distribution and the target
+    net's greedy next action."""
+    B, A, N = _c51_shape(logits, atoms, "logits")
+    dev = logits.device
+    f = torch.float32
+    if dlogits is None:
+        dlogits = torch.empty_like(logits)
+    if stats is None:
+        stats = torch.empty(2, dtype=f, device=dev)
+    call("ocppo_c51_loss_fwd_bwd", _stream(dev), _check(logits, "logits", f, dev),
+         _check(logits_next, "logits_next", f, dev, B * A * N), _check(atoms, "atoms", f, dev),
+         _check(actions, "actions", torch.int64, dev, B), _check(rewards, "rewards", f, dev, B),
+         _check(dones, "dones", f, dev, B), B, A, N, float(gamma), float(v_min), float(v_max),
+         _check(dlogits, "dlogits", f, dev, B * A * N), _check(stats, "stats", f, dev, 2),
+         _opt(target_pmfs, "target_pmfs", f, dev, B * N),
+         _opt(next_action, "next_action", torch.int64, dev, B))
+    return stats, dlogits
