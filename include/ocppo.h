@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCPPO_ABI_VERSION 29
+#define OCPPO_ABI_VERSION 30
 
 /* status codes */
 #define OCPPO_OK 0
@@ -859,6 +859,124 @@ OCPPO_API int ocppo_c51_epsilon_greedy(ocppo_stream_t stream, const float* logit
                                        uint64_t seed, const int64_t* step, int64_t step_offset,
                                        double start_e, double end_e, double duration,
                                        int64_t* actions, float* epsilon_out, float* q_out);
+
+/* ---------------------------------------------------------------------------------------------
+ * Rainbow (cleanrl/rainbow_atari_oc.py; ABI 30), part 1: the prioritized n-step replay
+ * (SumSegmentTree :338-369 + PrioritizedReplayBuffer :395-499) with all of its state in HBM, for
+ * num_envs == 1 as the script asserts (:513). The reference walks a numpy sum tree in Python, one
+ * host step per sampled element and per updated priority, and copies loss_per_sample to the host
+ * on every train step (:704); these entries read and write device memory only, allocate nothing,
+ * and replay from a hipGraph. The MinSegmentTree (:373-392) is written and never read in the
+ * reference (min() has no caller), so it does not exist here.
+ *   rb_obs, rb_next_obs : [capacity, D] in rb_dtype (both rows are stored, as :446-447: the
+ *                 n-step next observation is not the next slot's)
+ *   rb_actions i64, rb_rewards f32, rb_dones f32 (0 / 1) : [capacity]
+ *   tree        : f32 [2 * capacity - 1], root 0, children of i at 2i + 1 and 2i + 2, the leaf of
+ *                 slot k at k + capacity - 1; capacity >= 2, any value
+ *   state       : i64 [8] = {pos, size, max_priority (f32 in the low 4 bytes; initialise to
+ *                 1.0f), n-step ring fill, n-step ring head, 0, 0, 0}
+ *   ring_*      : the deque(maxlen=n_step) of :420: ring_obs / ring_next_obs [n_step, D] in
+ *                 rb_dtype, ring_actions i64, ring_rewards f32, ring_dones f32 [n_step]; n_step <= 8
+ *   workspace   : ocppo_per_workspace_bytes() bytes, zeroed once
+ *
+ * ocppo_per_add (:435-460 with _get_n_step_info :422-433), one launch: pushes (obs, action,
+ * reward, next_obs, done) of the single env into the ring; with fewer than n_step entries nothing
+ * else is written. Otherwise the row at pos receives the first entry's obs and action, the
+ * n-step reward sum_i gamma_pows[i] * r_i accumulated term by term in f64 up to and including the
+ * first done entry (the loop passes float64 reward arrays) and rounded to f32 on the store, and
+ * the next obs and done of the first done entry, or else of the last; its leaf becomes
+ * max_priority ** alpha and its ancestors are recomputed; pos and size advance; a done row
+ * clears the ring (so the n - 1 starts at the end of an episode are dropped, as in the
+ * reference). gamma_pows is HOST memory: the n_step values gamma ** i formed in Python.
+ *
+ * ocppo_per_update_priorities (:492-499), one launch: p = |loss_per_sample| + f32(eps);
+ * max_priority = max(max_priority, max p); leaf[indices[i]] = p_i ** alpha (of a repeated index
+ * the last occurrence, the reference's order); then every ancestor of a touched leaf is
+ * recomputed as f32(left + right), level by level from the deepest, which is what the
+ * reference's sequential updates leave. B <= 1024; an index outside [0, capacity) is ignored.
+ *
+ * ocppo_per_sample (:462-490), two launches (indices + weights, row gather): segment =
+ * total / B in f32; upperbound_i uniform in [segment * i, segment * (i + 1)) in f64 from the
+ * counter-based stream of (seed, counter[0]), or upperbounds_in[i] when given; index =
+ * retrieve(upperbound) (:359-369) in f64 against the f32 nodes; probs = the leaf; weights =
+ * (size * probs / total) ** -beta divided by the batch maximum, with beta = min(1, beta0 +
+ * (step[0] + step_offset) * (1 - beta0) / total_timesteps) (:611-614; beta0 when step is NULL).
+ * counter[0] advances by one.
+ *   obs_out, next_obs_out : [B, D] f32;  actions_out i64, rewards_out, dones_out, weights_out
+ *   f32, indices_out i64 : [B];  probs_out f32 [B], upperbounds_out f64 [B], beta_out f32 [1]
+ *   or NULL.  B <= 1024.
+ * ------------------------------------------------------------------------------------------- */
+OCPPO_API size_t ocppo_per_workspace_bytes(void);
+OCPPO_API int ocppo_per_add(ocppo_stream_t stream, const void* obs, const void* next_obs,
+                            int obs_dtype, const int64_t* action, const float* reward,
+                            const float* done, int64_t D, int64_t n_step,
+                            const double* gamma_pows, double alpha, int64_t* state,
+                            int64_t capacity, void* rb_obs, void* rb_next_obs, int rb_dtype,
+                            int64_t* rb_actions, float* rb_rewards, float* rb_dones, float* tree,
+                            void* ring_obs, void* ring_next_obs, int64_t* ring_actions,
+                            float* ring_rewards, float* ring_dones, void* workspace);
+OCPPO_API int ocppo_per_update_priorities(ocppo_stream_t stream, const int64_t* indices,
+                                          const float* loss_per_sample, int64_t B, double eps,
+                                          double alpha, int64_t* state, int64_t capacity,
+                                          float* tree);
+OCPPO_API int ocppo_per_sample(ocppo_stream_t stream, uint64_t seed, int64_t* counter,
+                               const int64_t* state, const int64_t* step, int64_t step_offset,
+                               double beta0, double total_timesteps, int64_t capacity, int64_t D,
+                               const void* rb_obs, const void* rb_next_obs, int rb_dtype,
+                               const int64_t* rb_actions, const float* rb_rewards,
+                               const float* rb_dones, const float* tree, int64_t B,
+                               const double* upperbounds_in, float* obs_out, float* next_obs_out,
+                               int64_t* actions_out, float* rewards_out, float* dones_out,
+                               int64_t* indices_out, float* weights_out, float* probs_out,
+                               double* upperbounds_out, float* beta_out);
+
+/* ---------------------------------------------------------------------------------------------
+ * Rainbow, part 2: the train step's loss block :655-701 and its backward as ONE launch, and the
+ * acting step :617-620. The networks (NoisyDuelingDistributionalNetwork, :283-327, and
+ * architectures/rainbow.py's NoisyDuelingDistributionalPPObj) end in
+ *   q_atoms = value + advantage - advantage.mean(dim=1, keepdim=True); softmax(q_atoms, dim=2)
+ * so these entries take the RAW head outputs value [rows, N] and advantage [rows, A * N] and form
+ * the dueling combine and the softmax themselves. support [N] is the registered buffer.
+ * 2 <= N <= 128, 1 <= A <= 18.
+ *
+ * ocppo_rainbow_loss_fwd_bwd (one workgroup, no float atomics, no workspace, bitwise repeatable,
+ * graph-replay safe: every output is fully rewritten):
+ *   value, advantage                     : q_network on observations
+ *   value/advantage_next_online          : q_network on next_observations (double Q, :664-667)
+ *   value/advantage_next_target          : target_network on next_observations (:657)
+ *   actions [B] i64; rewards, dones, weights [B] f32
+ *   gamma_n     : args.gamma ** args.n_step, formed by the host (:672)
+ *   best action = first argmax_a of the ONLINE net's expected value; p' = the TARGET net's pmf
+ *                 at that action (:667-669)
+ *   next_atoms  = r + (f32(gamma_n) * support) * (1 - d); tz = clamp(next_atoms, v_min, v_max);
+ *                 b = (tz - v_min) / f32(delta_z), delta_z = (v_max - v_min) / (N - 1) as the
+ *                 modules' __init__ forms it (NOT the buffer's spacing); l = floor(b), u =
+ *                 ceil(b), clamped to [0, N - 1]; target[l] += (u + (l == b) - b) * p' for every
+ *                 source atom in ascending order, then target[u] += (b - l) * p' likewise
+ *                 (:678-692, index_add_'s CPU order)
+ *   p = the online pmf of the taken action; loss_per_sample_b = -sum_k target_k *
+ *                 log(clamp(p_k, 1e-5, 1 - 1e-5)); loss = mean_b(loss_per_sample_b * weights_b)
+ *   dvalue [B, N], dadvantage [B, A * N] : d loss / d (value, advantage) through the clamp mask,
+ *                 the softmax and the dueling combine; rows of actions not taken receive the
+ *                 -1 / A share only; every element is written
+ *   loss_per_sample [B] (the new priorities, :704-705)
+ *   stats       : [2] = {losses/td_loss, losses/q_values = mean_b sum_k p_k * support_k} (:708-713)
+ *   target_pmfs : [B, N] or NULL;  best_actions : [B] i64 or NULL
+ *
+ * ocppo_rainbow_greedy (:617-620): actions[e] = first argmax_a sum_k q_dist[e, a, k] * support_k,
+ * one wave per env, no epsilon.  q_out : [E, A] or NULL.
+ * ------------------------------------------------------------------------------------------- */
+OCPPO_API int ocppo_rainbow_loss_fwd_bwd(
+    ocppo_stream_t stream, const float* value, const float* advantage,
+    const float* value_next_online, const float* advantage_next_online,
+    const float* value_next_target, const float* advantage_next_target, const float* support,
+    const int64_t* actions, const float* rewards, const float* dones, const float* weights,
+    int64_t B, int64_t A, int64_t N, double gamma_n, double v_min, double v_max, float* dvalue,
+    float* dadvantage, float* loss_per_sample, float* stats, float* target_pmfs,
+    int64_t* best_actions);
+OCPPO_API int ocppo_rainbow_greedy(ocppo_stream_t stream, const float* value,
+                                   const float* advantage, const float* support, int64_t E,
+                                   int64_t A, int64_t N, int64_t* actions, float* q_out);
 
 /* ---------------------------------------------------------------------------------------------
  * Synthetic device-resident env (benchmark / test harness; ALE and OCAtari are not available).

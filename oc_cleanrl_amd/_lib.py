@@ -22,7 +22,7 @@ LIB_PATH = Path(os.environ.get("OCPPO_LIB", PKG / "lib" / "libocppo_hip.so"))
 HEADER = PKG.parent / "include" / "ocppo.h"
 
 # constants mirrored from include/ocppo.h (checked against the header by tests/test_abi.py)
-OCPPO_ABI_VERSION = 29
+OCPPO_ABI_VERSION = 30
 OCPPO_OK, OCPPO_E_INVALID, OCPPO_E_LAUNCH, OCPPO_E_WORKSPACE = 0, 1, 2, 3
 OCPPO_F32, OCPPO_BF16, OCPPO_U8 = 0, 1, 2
 OCPPO_X6_MBITS_ROWS = 2
@@ -89,6 +89,15 @@ SIGNATURES: dict[str, tuple[type, list]] = {
     "ocppo_td_loss_fwd_bwd": (I, [P, P, P, P, P, P, I64, I64, D, P, P]),
     "ocppo_c51_loss_fwd_bwd": (I, [P, P, P, P, P, P, P, I64, I64, I64, D, D, D, P, P, P, P]),
     "ocppo_c51_epsilon_greedy": (I, [P, P, P, I64, I64, I64, U64, P, I64, D, D, D, P, P, P]),
+    "ocppo_per_workspace_bytes": (SZ, []),
+    "ocppo_per_add": (I, [P, P, P, I, P, P, P, I64, I64, P, D, P, I64, P, P, I, P, P, P, P, P, P,
+                          P, P, P, P]),
+    "ocppo_per_update_priorities": (I, [P, P, P, I64, D, D, P, I64, P]),
+    "ocppo_per_sample": (I, [P, U64, P, P, P, I64, D, D, I64, I64, P, P, I, P, P, P, P, I64, P, P,
+                             P, P, P, P, P, P, P, P, P]),
+    "ocppo_rainbow_loss_fwd_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, D, D, D,
+                                       P, P, P, P, P, P]),
+    "ocppo_rainbow_greedy": (I, [P, P, P, P, I64, I64, I64, P, P]),
     "ocppo_synth_env_step": (I, [P, U64, P, I64, P, I64, I64, I, P, P, P, P]),
     "ocppo_policy_head_env_step": (I, [P, P, I64, I64, P, P, P, P, P, P, I64, I64, I64, P, P, P,
                                        U64, P, I64, I64, P, P, P, P]),

@@ -11,13 +11,9 @@
 #include <math.h>
 
 #include "ocppo_common.h"
+#include "ocppo_distributional.h"
 
 namespace ocppo {
-
-constexpr int kC51MaxAtoms = 128;
-constexpr int kC51MaxActions = 18;
-constexpr int kC51LossWaves = 16;  // the loss kernel's single workgroup: 1024 threads
-constexpr int kC51Batch = 6;       // softmaxes a wave reduces side by side (independent chains)
 
 // the splitmix64 finaliser of ocppo_dqn.hip (epsilon_greedy_kernel's coin and random action)
 __device__ __forceinline__ uint64_t c51_mix64(uint64_t x) {
@@ -25,54 +21,6 @@ __device__ __forceinline__ uint64_t c51_mix64(uint64_t x) {
   x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
   x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
   return x ^ (x >> 31);
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, kWave));
-  return v;
-}
-
-// softmax over the N atoms of up to G consecutive [N] rows starting at `rows` (`valid` of them
-// exist; the others repeat the last one and are ignored by the caller), and each row's expected
-// value q = sum_k p_k * z_k (torch.softmax(dim=2); (pmfs * atoms).sum(2)). Called by a whole
-// wave; p0 / p1 are this lane's atoms `lane` and `lane + 64` (0 past N), q is the same in every
-// lane. The G chains are independent, so their butterflies overlap.
-template <int G>
-__device__ __forceinline__ void c51_softmax_q(const float* __restrict__ rows, int valid, int N,
-                                              int lane, float z0, float z1, float (&p0)[G],
-                                              float (&p1)[G], float (&q)[G]) {
-  const bool h0 = lane < N, h1 = lane + kWave < N;
-  float x0[G], x1[G], m[G], s[G];
-#pragma unroll
-  for (int g = 0; g < G; ++g) {
-    const float* row = rows + static_cast<int64_t>(g < valid ? g : valid - 1) * N;
-    x0[g] = h0 ? row[lane] : -INFINITY;
-    x1[g] = h1 ? row[lane + kWave] : -INFINITY;
-  }
-#pragma unroll
-  for (int g = 0; g < G; ++g) m[g] = wave_max(fmaxf(x0[g], x1[g]));
-#pragma unroll
-  for (int g = 0; g < G; ++g) {
-    x0[g] = h0 ? expf(x0[g] - m[g]) : 0.f;
-    x1[g] = h1 ? expf(x1[g] - m[g]) : 0.f;
-    s[g] = x0[g] + x1[g];
-  }
-#pragma unroll
-  for (int g = 0; g < G; ++g) s[g] = wave_sum(s[g]);
-#pragma unroll
-  for (int g = 0; g < G; ++g) {
-    p0[g] = x0[g] / s[g];
-    p1[g] = x1[g] / s[g];
-    q[g] = p0[g] * z0 + p1[g] * z1;
-  }
-#pragma unroll
-  for (int g = 0; g < G; ++g) q[g] = wave_sum(q[g]);
-}
-
-// torch.argmax's update rule on a running best (first maximum; a NaN beats every number)
-__device__ __forceinline__ bool c51_better(float v, float best) {
-  return v > best || (v != v && best == best);
 }
 
 // Fused C51 train-step loss (c51_atari_oc.py:339-359), forward and d loss / d logits, as ONE

@@ -226,10 +226,7 @@ class DQNTrainer:
         self.stacks = [torch.zeros((self.E,) + self.obs_shape, dtype=st, device=dev)
                        for _ in range(2)]
         self.net_obs = torch.zeros((self.E,) + self.obs_shape, dtype=f32, device=dev)
-        # SB3 keeps buffer_size // n_envs rows of n_envs transitions (buffers.py:185)
-        self.rb = ops.ReplayBuffer(max(a.buffer_size // self.E, 1), self.E, self.obs_shape, dev,
-                                   obs_dtype=st,
-                                   seed=a.seed)
+        self.rb = self._make_replay(st)
         self.actions = torch.zeros(self.E, dtype=torch.int64, device=dev)
         self.rew_out = torch.zeros(self.E, dtype=f32, device=dev)
         self.done_out = torch.zeros(self.E, dtype=f32, device=dev)
@@ -260,12 +257,18 @@ class DQNTrainer:
         frame = self.env.reset()
         ops.obs_reset(frame, self.stacks[0], self.net_obs)
 
-    # ---- what a learner on the same loop replaces (c51.C51Trainer) ------------------------------
+    # ---- what a learner on the same loop replaces (c51, rainbow) ---------------------------------
     def _make_net(self) -> nn.Module:
         return make_qnet(self.args, self.obs_shape, self.A)
 
     def _adam_eps(self) -> float:
         return 1e-8  # optim.Adam's default
+
+    def _make_replay(self, obs_dtype):
+        # SB3 keeps buffer_size // n_envs rows of n_envs transitions (buffers.py:185)
+        a = self.args
+        return ops.ReplayBuffer(max(a.buffer_size // self.E, 1), self.E, self.obs_shape, self.dev,
+                                obs_dtype=obs_dtype, seed=a.seed)
 
     def _act(self, k: int):
         """Greedy / random actions of global step chunk base + k + 1 from the whole network."""

@@ -2509,3 +2509,205 @@ def c51_loss_fwd_bwd(logits, logits_next, atoms, actions, rewards, dones, gamma:
          _opt(target_pmfs, "target_pmfs", f, dev, B * N),
          _opt(next_action, "next_action", torch.int64, dev, B))
     return stats, dlogits
+
+
+# ---------------------------------------------------------------------------------------------
+# Rainbow (rainbow_atari_oc.py): device prioritized n-step replay, fused double-Q projection +
+# weighted cross-entropy loss through the dueling heads, greedy acting
+# ---------------------------------------------------------------------------------------------
+PER_MAX_NSTEP, PER_MAX_BATCH = 8, 1024
+
+
+class PrioritizedReplay:
+    """PrioritizedReplayBuffer + SumSegmentTree (rainbow_atari_oc.py:338-499) in HBM for one env:
+    obs / next_obs rows [capacity, D] in an exact compact dtype, the f32 sum tree in the
+    reference's layout, the n-step ring, and a device state block {pos, size, max_priority, ring
+    fill, ring head}, so add / sample / update_priorities replay from a hipGraph. beta follows
+    the device step counter (`step` + step_offset) when sample() is given one."""
+
+    def __init__(self, capacity: int, obs_shape, device, n_step: int, gamma: float,
+                 alpha: float = 0.6, beta: float = 0.4, eps: float = 1e-6,
+                 total_timesteps: float = 1.0, obs_dtype=torch.uint8, seed: int = 0,
+                 num_envs: int = 1):
+        if num_envs != 1:
+            raise ValueError("PrioritizedReplay: vectorized envs are not supported (num_envs == 1)")
+        if not 1 <= int(n_step) <= PER_MAX_NSTEP:
+            raise ValueError(f"PrioritizedReplay: n_step={n_step}, need 1 <= n_step <= {PER_MAX_NSTEP}")
+        if int(capacity) < 2:
+            raise ValueError("PrioritizedReplay: capacity must be >= 2")
+        if obs_dtype not in _DTYPE_CODE:
+            raise ValueError("PrioritizedReplay: obs_dtype must be f32, bf16 or u8")
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise ValueError(f"PrioritizedReplay: HIP kernels need a GPU, got device {dev}")
+        self.capacity, self.n_step = int(capacity), int(n_step)
+        self.obs_shape = tuple(obs_shape)
+        self.D = 1
+        for d in self.obs_shape:
+            self.D *= d
+        self.device = dev
+        self.gamma, self.alpha, self.beta, self.eps = float(gamma), float(alpha), float(beta), float(eps)
+        self.total_timesteps = float(total_timesteps)
+        # the n_step powers gamma ** i in Python's arithmetic (:428)
+        self.gamma_pows = (ctypes.c_double * self.n_step)(*[self.gamma ** i for i in range(self.n_step)])
+        C, n, f, i64 = self.capacity, self.n_step, torch.float32, torch.int64
+        self.obs = torch.zeros((C,) + self.obs_shape, dtype=obs_dtype, device=dev)
+        self.next_obs = torch.zeros((C,) + self.obs_shape, dtype=obs_dtype, device=dev)
+        self.actions = torch.zeros(C, dtype=i64, device=dev)
+        self.rewards = torch.zeros(C, dtype=f, device=dev)
+        self.dones = torch.zeros(C, dtype=f, device=dev)
+        self.tree = torch.zeros(2 * C - 1, dtype=f, device=dev)
+        self.state = torch.zeros(8, dtype=i64, device=dev)
+        self.state.view(f)[4] = 1.0  # max_priority (:414)
+        self.ring_obs = torch.zeros((n,) + self.obs_shape, dtype=obs_dtype, device=dev)
+        self.ring_next_obs = torch.zeros((n,) + self.obs_shape, dtype=obs_dtype, device=dev)
+        self.ring_actions = torch.zeros(n, dtype=i64, device=dev)
+        self.ring_rewards = torch.zeros(n, dtype=f, device=dev)
+        self.ring_dones = torch.zeros(n, dtype=f, device=dev)
+        self.counter = torch.zeros(1, dtype=i64, device=dev)
+        self.beta_dev = torch.full((1,), self.beta, dtype=f, device=dev)
+        self.ws = torch.zeros(int(_lib.LIB.ocppo_per_workspace_bytes()), dtype=torch.uint8,
+                              device=dev)
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+
+    @property
+    def max_priority(self) -> float:
+        return float(self.state.view(torch.float32)[4])
+
+    def add(self, obs, next_obs, actions, rewards, dones):
+        """rb.add(obs, actions, rewards, real_next_obs, terminations) (:642) of the one env."""
+        dev, f = self.device, torch.float32
+        if not isinstance(obs, torch.Tensor) or obs.dtype not in _DTYPE_CODE or \
+                next_obs.dtype != obs.dtype:
+            raise ValueError("obs/next_obs must both be f32, bf16 or u8 tensors")
+        call("ocppo_per_add", _stream(dev), _check(obs, "obs", None, dev, self.D),
+             _check(next_obs, "next_obs", None, dev, self.D), _DTYPE_CODE[obs.dtype],
+             _check(actions, "actions", torch.int64, dev, 1), _check(rewards, "rewards", f, dev, 1),
+             _check(dones, "dones", f, dev, 1), self.D, self.n_step, self.gamma_pows, self.alpha,
+             self.state.data_ptr(), self.capacity, self.obs.data_ptr(), self.next_obs.data_ptr(),
+             _DTYPE_CODE[self.obs.dtype], self.actions.data_ptr(), self.rewards.data_ptr(),
+             self.dones.data_ptr(), self.tree.data_ptr(), self.ring_obs.data_ptr(),
+             self.ring_next_obs.data_ptr(), self.ring_actions.data_ptr(),
+             self.ring_rewards.data_ptr(), self.ring_dones.data_ptr(), self.ws.data_ptr())
+
+    def new_batch(self, batch_size: int, probs: bool = False, upperbounds: bool = False) -> dict:
+        B, dev, f = int(batch_size), self.device, torch.float32
+        out = {"observations": torch.zeros((B,) + self.obs_shape, device=dev),
+               "next_observations": torch.zeros((B,) + self.obs_shape, device=dev),
+               "actions": torch.zeros((B, 1), dtype=torch.int64, device=dev),
+               "rewards": torch.zeros((B, 1), device=dev), "dones": torch.zeros((B, 1), device=dev),
+               "indices": torch.zeros(B, dtype=torch.int64, device=dev),
+               "weights": torch.zeros((B, 1), dtype=f, device=dev)}
+        if probs:
+            out["probs"] = torch.zeros(B, dtype=f, device=dev)
+        if upperbounds:
+            out["upperbounds"] = torch.zeros(B, dtype=torch.float64, device=dev)
+        return out
+
+    def sample(self, batch_size: int, out: dict | None = None, step=None, step_offset: int = 0,
+               upperbounds_in=None):
+        """(:462-490) `out` (new_batch) receives observations, next_observations, actions,
+        rewards, dones, indices, weights and, where present, probs / upperbounds. beta =
+        min(1, self.beta + (step + step_offset) * (1 - self.beta) / total_timesteps), or
+        self.beta without `step`; upperbounds_in [B] f64 replaces the draws."""
+        dev, f = self.device, torch.float32
+        B = int(batch_size)
+        if not 1 <= B <= PER_MAX_BATCH:
+            raise ValueError(f"batch_size={B}: need 1 <= batch_size <= {PER_MAX_BATCH}")
+        if out is None:
+            out = self.new_batch(B)
+        n = B * self.D
+        call("ocppo_per_sample", _stream(dev), self.seed, self.counter.data_ptr(),
+             self.state.data_ptr(), _opt(step, "step", torch.int64, dev, 1), int(step_offset),
+             self.beta, self.total_timesteps, self.capacity, self.D, self.obs.data_ptr(),
+             self.next_obs.data_ptr(), _DTYPE_CODE[self.obs.dtype], self.actions.data_ptr(),
+             self.rewards.data_ptr(), self.dones.data_ptr(), self.tree.data_ptr(), B,
+             _opt(upperbounds_in, "upperbounds_in", torch.float64, dev, B),
+             _check(out["observations"], "observations", f, dev, n),
+             _check(out["next_observations"], "next_observations", f, dev, n),
+             _check(out["actions"], "actions", torch.int64, dev, B),
+             _check(out["rewards"], "rewards", f, dev, B), _check(out["dones"], "dones", f, dev, B),
+             _check(out["indices"], "indices", torch.int64, dev, B),
+             _check(out["weights"], "weights", f, dev, B),
+             _opt(out.get("probs"), "probs", f, dev, B),
+             _opt(out.get("upperbounds"), "upperbounds", torch.float64, dev, B),
+             self.beta_dev.data_ptr())
+        return out
+
+    def update_priorities(self, indices, loss_per_sample):
+        """(:492-499) straight from the loss kernel's device output."""
+        dev = self.device
+        B = indices.numel() if isinstance(indices, torch.Tensor) else 0
+        if not 1 <= B <= PER_MAX_BATCH:
+            raise ValueError(f"indices: need 1 <= B <= {PER_MAX_BATCH} elements")
+        call("ocppo_per_update_priorities", _stream(dev),
+             _check(indices, "indices", torch.int64, dev, B),
+             _check(loss_per_sample, "loss_per_sample", torch.float32, dev, B), B, self.eps,
+             self.alpha, self.state.data_ptr(), self.capacity, self.tree.data_ptr())
+
+
+def _rainbow_shape(value, advantage, support, name: str):
+    """(rows, A, N) of value [rows, N] / advantage [rows, A * N] against the [N] support."""
+    if not isinstance(support, torch.Tensor) or support.dim() != 1:
+        raise ValueError("support: expected the [N] support buffer")
+    N = support.shape[0]
+    if not 2 <= N <= C51_MAX_ATOMS:
+        raise ValueError(f"support: N={N}, need 2 <= N <= {C51_MAX_ATOMS}")
+    if not isinstance(value, torch.Tensor) or value.dim() != 2 or value.shape[1] != N or \
+            value.shape[0] < 1:
+        raise ValueError(f"{name}: value must be [rows >= 1, {N}]")
+    rows = value.shape[0]
+    if not isinstance(advantage, torch.Tensor) or advantage.dim() != 2 or \
+            advantage.shape[0] != rows or advantage.shape[1] % N or \
+            not 1 <= advantage.shape[1] // N <= C51_MAX_ACTIONS:
+        raise ValueError(f"{name}: advantage must be [{rows}, A * {N}] with 1 <= A <= "
+                         f"{C51_MAX_ACTIONS}")
+    return rows, advantage.shape[1] // N, N
+
+
+def rainbow_greedy(value, advantage, support, actions_out=None, q_out=None):
+    """argmax_a (softmax(value + advantage - mean_a advantage, atoms) * support).sum(atoms) in one
+    launch (rainbow_atari_oc.py:617-620), first maximum."""
+    E, A, N = _rainbow_shape(value, advantage, support, "rainbow_greedy")
+    dev, f = value.device, torch.float32
+    if actions_out is None:
+        actions_out = torch.empty(E, dtype=torch.int64, device=dev)
+    call("ocppo_rainbow_greedy", _stream(dev), _check(value, "value", f, dev),
+         _check(advantage, "advantage", f, dev), _check(support, "support", f, dev), E, A, N,
+         _check(actions_out, "actions", torch.int64, dev, E), _opt(q_out, "q_out", f, dev, E * A))
+    return actions_out
+
+
+def rainbow_loss_fwd_bwd(value, advantage, value_next_online, advantage_next_online,
+                         value_next_target, advantage_next_target, support, actions, rewards,
+                         dones, weights, gamma_n: float, v_min: float, v_max: float, dvalue=None,
+                         dadvantage=None, loss_per_sample=None, stats=None, target_pmfs=None,
+                         best_actions=None):
+    """rainbow_atari_oc.py:655-701 and its backward in one launch, on the raw head outputs of the
+    three forwards. Returns (stats [2] = {loss, mean expected Q of the taken actions},
+    loss_per_sample [B], dvalue [B, N], dadvantage [B, A * N])."""
+    B, A, N = _rainbow_shape(value, advantage, support, "rainbow_loss_fwd_bwd")
+    dev, f = value.device, torch.float32
+    if dvalue is None:
+        dvalue = torch.empty_like(value)
+    if dadvantage is None:
+        dadvantage = torch.empty_like(advantage)
+    if loss_per_sample is None:
+        loss_per_sample = torch.empty(B, dtype=f, device=dev)
+    if stats is None:
+        stats = torch.empty(2, dtype=f, device=dev)
+    call("ocppo_rainbow_loss_fwd_bwd", _stream(dev), _check(value, "value", f, dev),
+         _check(advantage, "advantage", f, dev),
+         _check(value_next_online, "value_next_online", f, dev, B * N),
+         _check(advantage_next_online, "advantage_next_online", f, dev, B * A * N),
+         _check(value_next_target, "value_next_target", f, dev, B * N),
+         _check(advantage_next_target, "advantage_next_target", f, dev, B * A * N),
+         _check(support, "support", f, dev), _check(actions, "actions", torch.int64, dev, B),
+         _check(rewards, "rewards", f, dev, B), _check(dones, "dones", f, dev, B),
+         _check(weights, "weights", f, dev, B), B, A, N, float(gamma_n), float(v_min),
+         float(v_max), _check(dvalue, "dvalue", f, dev, B * N),
+         _check(dadvantage, "dadvantage", f, dev, B * A * N),
+         _check(loss_per_sample, "loss_per_sample", f, dev, B), _check(stats, "stats", f, dev, 2),
+         _opt(target_pmfs, "target_pmfs", f, dev, B * N),
+         _opt(best_actions, "best_actions", torch.int64, dev, B))
+    return stats, loss_per_sample, dvalue, dadvantage

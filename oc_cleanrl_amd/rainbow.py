@@ -1,0 +1,328 @@
+"""Rainbow learner of cleanrl/rainbow_atari_oc.py on HBM-resident state.
+
+The reference's third off-policy learner runs on the loop of dqn_atari_oc.py with these pieces
+changed: a noisy dueling distributional network (NoisyLinear heads, :239-327, and the object
+network of architectures/rainbow.py), greedy acting with the noise left on (:617-620, no epsilon),
+a prioritized n-step replay kept on the HOST (a numpy sum tree walked by Python loops, :338-499),
+double-Q + n-step categorical projection + importance-weighted cross entropy (:655-701), new
+priorities from the per-sample loss through `.cpu().numpy()` on every train step (:704-705), Adam
+with eps = 1.5e-4 (:587) and the tau target update (:725-728). No VecNormalize.
+
+`RainbowTrainer` is `dqn.DQNTrainer` with those pieces replaced:
+  ops.rainbow_greedy         dueling combine + softmax + expected Q + first maximum, one launch
+  ops.PrioritizedReplay      the replay, the sum tree and the n-step ring in HBM: add, sample
+                             (stratified draws, f64 descent, weights, beta from the device step
+                             counter) and update_priorities without a host step
+  ops.rainbow_loss_fwd_bwd   :655-701 and its backward to the two heads' raw outputs, one launch
+everything else (env, store, FlatAdam, the fill / train chunk hipGraphs) is the DQN learner's.
+
+The trunks run on the fused Linear / convolution path (agents.fused_trunk); the noisy heads are
+torch ops (mu + sigma * eps, then the Linear), and their noise is torch's normal_() on the full
+matrices, as in the reference.
+"""
+from __future__ import annotations
+
+import json
+import math
+import time
+from dataclasses import asdict, dataclass
+from pathlib import Path
+from typing import Optional
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import ops
+from .agents import Predictor, fused_trunk, layer_init
+from .args import OBS_MODES, parse_dataclass
+from .dqn import DQNTrainer
+
+
+@dataclass
+class RainbowArgs:
+    """The flags of rainbow_atari_oc.py:56-158 (same names and defaults) + this build's
+    additions."""
+    exp_name: str = "rainbow_atari_oc"
+    seed: int = 1
+    torch_deterministic: bool = True
+    cuda: bool = True
+    env_id: str = "ALE/Pong-v5"
+    obs_mode: str = "dqn"
+    buffer_window_size: int = 4
+    backend: str = "Synthetic"  # reference: HackAtari (ALE not available here)
+    modifs: str = ""
+    new_rf: str = ""
+    frameskip: int = 4
+    masked_wrapper: str = ""
+    track: bool = False
+    wandb_project_name: str = "OC-Transformer"
+    wandb_entity: str = "AIML_OC"
+    wandb_dir: Optional[str] = None
+    capture_video: bool = False
+    ckpt: str = ""
+    logging_level: int = 40
+    author: str = "JB"
+    save_model: bool = False
+    upload_model: bool = False
+    hf_entity: str = ""
+    architecture: str = "Rainbow"
+    total_timesteps: int = 10_000_000
+    learning_rate: float = 0.0000625
+    num_envs: int = 1
+    buffer_size: int = 1_000_000
+    gamma: float = 0.99
+    tau: float = 1.0
+    target_network_frequency: int = 8000
+    batch_size: int = 32
+    start_e: float = 1
+    end_e: float = 0.01
+    exploration_fraction: float = 0.10
+    learning_starts: int = 80000
+    train_frequency: int = 4
+    n_step: int = 3
+    prioritized_replay_alpha: float = 0.5
+    prioritized_replay_beta: float = 0.4
+    prioritized_replay_eps: float = 1e-6
+    n_atoms: int = 51
+    v_min: float = -10
+    v_max: float = 10
+    encoder_dims: tuple = (256, 512, 1024, 512)
+    decoder_dims: tuple = (512,)
+
+    # [oc_cleanrl_amd] additions (as DQNArgs)
+    num_features: int = 12      # object-vector width F per frame (synthetic obj env)
+    obs_storage: str = "auto"   # replay obs dtype: auto (u8 pixels / bf16 objects) | f32 | bf16 | u8
+    cuda_graphs: bool = True
+    gemm_table: bool = False
+    vecnorm_reward: bool = False  # rainbow_atari_oc.py applies no VecNormalize
+    log_dir: str = "runs"
+    log_every: int = 100        # the reference logs td_loss / q_values / beta every 100 steps
+
+
+class NoisyLinear(nn.Module):
+    """:239-279 / architectures/rainbow.py:12-52. mu uniform in +-1 / sqrt(in), sigma constant,
+    and a full [out, in] matrix of independent normal noise (not the factorised form)."""
+
+    def __init__(self, in_features, out_features, std_init=0.5):
+        super().__init__()
+        self.in_features, self.out_features, self.std_init = in_features, out_features, std_init
+        self.weight_mu = nn.Parameter(torch.empty(out_features, in_features))
+        self.weight_sigma = nn.Parameter(torch.empty(out_features, in_features))
+        self.register_buffer("weight_epsilon", torch.empty(out_features, in_features))
+        self.bias_mu = nn.Parameter(torch.empty(out_features))
+        self.bias_sigma = nn.Parameter(torch.empty(out_features))
+        self.register_buffer("bias_epsilon", torch.empty(out_features))
+        self.reset_parameters()
+        self.reset_noise()
+
+    def reset_parameters(self):
+        bound = 1 / math.sqrt(self.in_features)
+        self.weight_mu.data.uniform_(-bound, bound)
+        self.weight_sigma.data.fill_(self.std_init / math.sqrt(self.in_features))
+        self.bias_mu.data.uniform_(-bound, bound)
+        self.bias_sigma.data.fill_(self.std_init / math.sqrt(self.out_features))
+
+    def reset_noise(self):
+        self.weight_epsilon.normal_()
+        self.bias_epsilon.normal_()
+
+    def forward(self, x):
+        if not self.training:
+            return F.linear(x, self.weight_mu, self.bias_mu)
+        return F.linear(x, self.weight_mu + self.weight_sigma * self.weight_epsilon,
+                        self.bias_mu + self.bias_sigma * self.bias_epsilon)
+
+
+class NoisyDuelingDistributionalNetwork(Predictor):
+    """:283-327: NatureCNN trunk, noisy value [N] and advantage [A * N] heads, the dueling combine
+    and a softmax per action over the registered `support`."""
+
+    def __init__(self, obs_shape, n_actions, n_atoms, v_min, v_max):
+        super().__init__()
+        self._set_support(n_actions, n_atoms, v_min, v_max)
+        self.network = nn.Sequential(
+            nn.Conv2d(obs_shape[0], 32, 8, stride=4), nn.ReLU(),
+            nn.Conv2d(32, 64, 4, stride=2), nn.ReLU(),
+            nn.Conv2d(64, 64, 3, stride=1), nn.ReLU(),
+            nn.Flatten())
+        self._set_heads(3136)
+
+    def _set_support(self, n_actions, n_atoms, v_min, v_max):
+        self.n_atoms, self.v_min, self.v_max = n_atoms, v_min, v_max
+        self.delta_z = (v_max - v_min) / (n_atoms - 1)
+        self.n_actions = n_actions
+        self.register_buffer("support", torch.linspace(v_min, v_max, n_atoms))
+
+    def _set_heads(self, in_dim):
+        self.value_head = nn.Sequential(NoisyLinear(in_dim, 512), nn.ReLU(),
+                                        NoisyLinear(512, self.n_atoms))
+        self.advantage_head = nn.Sequential(NoisyLinear(in_dim, 512), nn.ReLU(),
+                                            NoisyLinear(512, self.n_atoms * self.n_actions))
+
+    def heads(self, x):
+        """The raw head outputs (value [len(x), N], advantage [len(x), A * N]) with the trunk on
+        the fused Linear / convolution path (same math as forward up to the dueling combine)."""
+        h = fused_trunk(self.network, x / 255.0)
+        return self.value_head(h), self.advantage_head(h)
+
+    def forward(self, x):
+        h = self.network(x / 255.0)
+        value = self.value_head(h).view(-1, 1, self.n_atoms)
+        advantage = self.advantage_head(h).view(-1, self.n_actions, self.n_atoms)
+        q_atoms = value + advantage - advantage.mean(dim=1, keepdim=True)
+        return F.softmax(q_atoms, dim=2)
+
+    def reset_noise(self):
+        for head in (self.value_head, self.advantage_head):
+            for layer in head:
+                if isinstance(layer, NoisyLinear):
+                    layer.reset_noise()
+
+    def predict(self, x, states=None, **_):
+        with torch.no_grad():
+            dev = self.support.device
+            q = (self.forward(torch.as_tensor(np.asarray(x), dtype=torch.float32, device=dev))
+                 * self.support).sum(2)
+            return np.argmax(q.cpu().numpy(), axis=1), states
+
+
+class NoisyDuelingDistributionalPPObj(NoisyDuelingDistributionalNetwork):
+    """architectures/rainbow.py:55-106: the PPObj trunk (per-frame Linear encoder, Flatten, Linear
+    decoder, layer_init) under the same heads; the input is divided by 255 here too."""
+
+    def __init__(self, obs_shape, n_actions, n_atoms, v_min, v_max, encoder_dims=(128, 64),
+                 decoder_dims=(32,)):
+        Predictor.__init__(self)
+        self._set_support(n_actions, n_atoms, v_min, v_max)
+        layers, d = [], obs_shape[-1]
+        for l in encoder_dims:
+            layers += [layer_init(nn.Linear(d, l)), nn.ReLU()]
+            d = l
+        layers.append(nn.Flatten())
+        d *= int(np.prod(obs_shape[:-1]))
+        for l in decoder_dims:
+            layers += [layer_init(nn.Linear(d, l)), nn.ReLU()]
+            d = l
+        self.network = nn.Sequential(*layers)
+        self._set_heads(d)
+
+
+def make_rainbow_net(args: RainbowArgs, obs_shape, n_actions) -> nn.Module:
+    if args.obs_mode == "obj":  # :578-583
+        return NoisyDuelingDistributionalPPObj(obs_shape, n_actions, args.n_atoms, args.v_min,
+                                               args.v_max, encoder_dims=args.encoder_dims,
+                                               decoder_dims=args.decoder_dims)
+    return NoisyDuelingDistributionalNetwork(obs_shape, n_actions, args.n_atoms, args.v_min,
+                                             args.v_max)
+
+
+class RainbowTrainer(DQNTrainer):
+    """DQNTrainer's loop (env step, store, replay add, chunk graphs) with the Rainbow network,
+    greedy acting, the prioritized n-step replay and the Rainbow train step."""
+
+    def __init__(self, args: RainbowArgs, device, log: bool = True):
+        if args.num_envs != 1:  # :513
+            raise ValueError("vectorized envs are not supported at the moment (num_envs == 1)")
+        if not (2 <= args.n_atoms <= ops.C51_MAX_ATOMS):
+            raise ValueError(f"n_atoms={args.n_atoms}: need 2 <= n_atoms <= {ops.C51_MAX_ATOMS}")
+        super().__init__(args, device, log)
+        if self.A > ops.C51_MAX_ACTIONS:
+            raise ValueError(f"{self.A} actions: the Rainbow kernels take at most "
+                             f"{ops.C51_MAX_ACTIONS}")
+        self.fused_act = False  # DQN's Q-head launch does not apply: acting is self._act
+        B, N, f = args.batch_size, args.n_atoms, torch.float32
+        self.batch = self.rb.new_batch(B)
+        self.dvalue = torch.zeros((B, N), dtype=f, device=self.dev)
+        self.dadvantage = torch.zeros((B, self.A * N), dtype=f, device=self.dev)
+        self.loss_per_sample = torch.zeros(B, dtype=f, device=self.dev)
+        self.gamma_n = args.gamma ** args.n_step  # :672
+
+    def _make_net(self) -> nn.Module:
+        return make_rainbow_net(self.args, self.obs_shape, self.A)
+
+    def _adam_eps(self) -> float:
+        return 1.5e-4  # :587
+
+    def _make_replay(self, obs_dtype):
+        a = self.args
+        return ops.PrioritizedReplay(a.buffer_size, self.obs_shape, self.dev, a.n_step, a.gamma,
+                                     a.prioritized_replay_alpha, a.prioritized_replay_beta,
+                                     a.prioritized_replay_eps, total_timesteps=a.total_timesteps,
+                                     obs_dtype=obs_dtype, seed=a.seed, num_envs=a.num_envs)
+
+    def _act(self, k: int):
+        """:617-620 — greedy on the expected value, the noise left on (no .eval())."""
+        value, advantage = self.q.heads(self.net_obs)
+        ops.rainbow_greedy(value, advantage, self.q.support, self.actions)
+
+    def _train_step(self):
+        """:650-722 — new noise for both nets, sample, three forwards, the fused loss, new
+        priorities from its per-sample output, backward through both heads, Adam."""
+        a = self.args
+        self.q.reset_noise()
+        self.target.reset_noise()
+        # beta of this global step (:611-614): the chunk base is already advanced
+        d = self.rb.sample(a.batch_size, out=self.batch, step=self.step_dev)
+        with torch.no_grad():
+            v_nt, a_nt = self.target.heads(d["next_observations"])
+            v_no, a_no = self.q.heads(d["next_observations"])
+        value, advantage = self.q.heads(d["observations"])
+        ops.rainbow_loss_fwd_bwd(value.detach(), advantage.detach(), v_no, a_no, v_nt, a_nt,
+                                 self.q.support, d["actions"], d["rewards"], d["dones"],
+                                 d["weights"], self.gamma_n, a.v_min, a.v_max,
+                                 dvalue=self.dvalue, dadvantage=self.dadvantage,
+                                 loss_per_sample=self.loss_per_sample, stats=self.td_stats)
+        self.rb.update_priorities(d["indices"], self.loss_per_sample)  # :704-705
+        self.opt.zero_grad()  # the heads' gradients accumulate (torch ops)
+        torch.autograd.backward([value, advantage], [self.dvalue, self.dadvantage])
+        self.opt.step()
+
+    def metrics(self) -> dict:
+        st = self.td_stats.tolist()
+        ep_ret, ep_len, ep_n = self.env.pop_episode_stats()
+        m = {"losses/td_loss": st[0], "losses/q_values": st[1],
+             "charts/beta": float(self.rb.beta_dev)}
+        if ep_n > 0:
+            m["charts/episodic_return"] = ep_ret / ep_n
+            m["charts/episodic_length"] = ep_len / ep_n
+        return m
+
+
+def run_rainbow(args: RainbowArgs, device=None) -> RainbowTrainer:
+    device = device or torch.device("cuda:0")
+    tr = RainbowTrainer(args, device)
+    run_name = f"{args.env_id}__{args.exp_name}__{args.seed}__{int(time.time())}".replace("/", "_")
+    run_dir = Path(args.log_dir) / run_name
+    run_dir.mkdir(parents=True, exist_ok=True)
+    (run_dir / "args.json").write_text(json.dumps(asdict(args), indent=1, default=str))
+    start = time.time()
+    chunk = max(args.train_frequency, args.log_every - args.log_every % args.train_frequency)
+    with open(run_dir / "metrics.jsonl", "w") as w:
+        while tr.global_step < args.total_timesteps:
+            n = min(chunk, args.total_timesteps - tr.global_step)
+            n -= n % args.train_frequency if tr._graphable() else 0
+            if n <= 0:
+                break
+            tr.steps(n)
+            m = tr.metrics()
+            m["charts/SPS"] = int(tr.global_step / (time.time() - start))
+            m["global_step"] = tr.global_step
+            w.write(json.dumps(m) + "\n")
+    # :734-739 (the reference always writes the final model)
+    torch.save(tr.checkpoint(), run_dir / f"{args.exp_name}.cleanrl_model")
+    return tr
+
+
+def main(argv=None):
+    args = parse_dataclass(RainbowArgs, argv, None,
+                           "oc_cleanrl_amd Rainbow (rainbow_atari_oc.py surface)")
+    if args.obs_mode not in OBS_MODES:
+        raise SystemExit(f"bad obs_mode {args.obs_mode}")
+    tr = run_rainbow(args)
+    print({k: round(v, 5) for k, v in tr.metrics().items()})
+
+
+if __name__ == "__main__":
+    main()

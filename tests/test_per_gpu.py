@@ -1,0 +1,265 @@
+"""ops.PrioritizedReplay (ocppo_per_add / _sample / _update_priorities) on the GPU against the
+fixtures made from the reference's PrioritizedReplayBuffer and against rainbow_util's numpy
+restatement of it (validated on those fixtures by test_rainbow_cpu.py)."""
+import numpy as np
+import pytest
+import torch
+
+from rainbow_util import (ADDSEQ_FIXTURES, F32_FLOOR, SAMPLE_FIXTURES, PerOracle,
+                          check_elementwise, fixture, per_weights, retrieve, strata,
+                          tree_is_consistent)
+
+pytestmark = pytest.mark.gpu
+f32 = np.float32
+
+
+def make(dev, capacity, obs_shape, n_step=1, gamma=0.99, alpha=0.5, seed=7, **kw):
+    from oc_cleanrl_amd import ops
+
+    return ops.PrioritizedReplay(capacity, obs_shape, dev, n_step, gamma, alpha, 0.4, 1e-6,
+                                 obs_dtype=torch.uint8, seed=seed, **kw)
+
+
+def dev_add(rb, obs, action, reward, next_obs, done):
+    dev = rb.device
+    rb.add(torch.from_numpy(np.ascontiguousarray(obs)).to(dev)[None],
+           torch.from_numpy(np.ascontiguousarray(next_obs)).to(dev)[None],
+           torch.tensor([int(action)], device=dev), torch.tensor([float(reward)], device=dev),
+           torch.tensor([float(done)], device=dev))
+
+
+def download(rb) -> dict:
+    st = rb.state.cpu()
+    return dict(obs=rb.obs.cpu().numpy(), next_obs=rb.next_obs.cpu().numpy(),
+                actions=rb.actions.cpu().numpy(), rewards=rb.rewards.cpu().numpy(),
+                dones=rb.dones.cpu().numpy() != 0, tree=rb.tree.cpu().numpy(), pos=int(st[0]),
+                size=int(st[1]), max_priority=st.view(torch.float32)[4].numpy().copy())
+
+
+def bits(x) -> int:
+    return int(np.asarray(x, f32).view(np.uint32))
+
+
+def check_tree(tree, capacity, ref_tree, leaf64, what):
+    """Leaves: zero where the reference's are, else the per-element rule against the f64 twin;
+    inner nodes: f32(left + right) of the device's OWN children, bitwise; and the whole tree
+    bitwise where every leaf equals the reference's. Returns True in that case."""
+    leaves, ref = tree[capacity - 1:], ref_tree[capacity - 1:]
+    assert np.array_equal(leaves == 0, ref == 0), what
+    nz = ref != 0
+    if nz.any():
+        check_elementwise(leaves[nz], ref[nz], leaf64[nz], what)
+    assert tree_is_consistent(tree, capacity), what
+    same = np.array_equal(leaves, ref)
+    if same:
+        assert np.array_equal(tree, ref_tree), what
+    return same
+
+
+@pytest.mark.parametrize("name", ADDSEQ_FIXTURES)
+def test_add_sequences_and_updates_match_reference(dev, name):
+    z = fixture(f"per_addseq_{name}")
+    C, alpha, eps = int(z["capacity"]), float(z["alpha"]), float(z["eps"])
+    rb = make(dev, C, z["obs"].shape[2:], int(z["n_step"]), float(z["gamma"]), alpha)
+    upd = {int(z[f"upd{j}_after_add"]): j for j in range(int(z["n_updates"]))}
+    leaf64 = np.zeros(C)
+    exact = 0
+    for t in range(len(z["pos"])):
+        before = int(z["pos"][t - 1]) if t else 0
+        dev_add(rb, z["in_obs"][t], z["in_action"][t], z["in_reward"][t], z["in_next_obs"][t],
+                z["in_done"][t])
+        d = download(rb)
+        for key in ("obs", "next_obs", "actions", "rewards", "dones"):
+            assert np.array_equal(d[key], z[key][t]), (key, t)  # bitwise
+        assert (d["pos"], d["size"]) == (int(z["pos"][t]), int(z["size"][t])), t
+        assert bits(d["max_priority"]) == bits(z["max_priority"][t]), t
+        if int(z["pos"][t]) != before:  # a row was written: its leaf is max_priority ** alpha
+            leaf64[before] = float(np.float64(z["max_priority"][t])) ** alpha
+        exact += check_tree(d["tree"], C, z["tree"][t], leaf64, ("add", t))
+        if t <= min(upd):  # adds alone: max_priority is 1 and 1 ** alpha is exactly 1
+            assert np.array_equal(d["tree"], z["tree"][t]), t
+        if t in upd:
+            j = upd[t]
+            idx, pri = z[f"upd{j}_indices"], z[f"upd{j}_priorities"]
+            rb.update_priorities(torch.from_numpy(idx).to(dev), torch.from_numpy(pri).to(dev))
+            d = download(rb)
+            assert bits(d["max_priority"]) == bits(z[f"upd{j}_max_priority"]), j
+            for k, i in enumerate(idx):  # in order: the last occurrence wins
+                leaf64[i] = z[f"upd{j}_leaf64"][k]
+            exact += check_tree(d["tree"], C, z[f"upd{j}_tree"], leaf64, ("update", j))
+            assert idx[-1] == idx[0]  # the duplicated index
+            got = d["tree"][idx[-1] + C - 1]
+            want32 = (np.abs(pri[-1]) + f32(eps)) ** f32(alpha)
+            check_elementwise([got], [want32], [z[f"upd{j}_leaf64"][-1]], "duplicate")
+    assert exact > 10  # the bitwise whole-tree comparison did run
+
+
+@pytest.mark.parametrize("name", SAMPLE_FIXTURES)
+def test_sample_with_given_upperbounds_matches_reference(dev, name):
+    z = fixture(f"per_sample_{name}")
+    C, B = int(z["capacity"]), int(z["B"])
+    rb = make(dev, C, z["buf_obs"].shape[1:])
+    for t, key in ((rb.obs, "buf_obs"), (rb.next_obs, "buf_next_obs"), (rb.actions, "buf_actions"),
+                   (rb.rewards, "buf_rewards"), (rb.tree, "buf_tree")):
+        t.copy_(torch.from_numpy(z[key]))
+    rb.dones.copy_(torch.from_numpy(z["buf_dones"].astype(f32)))
+    rb.state[0], rb.state[1] = int(z["buf_pos"]), int(z["buf_size"])
+    ub = torch.from_numpy(z["upperbounds"]).to(dev)
+    for j in (0, 1):
+        rb.beta = float(z[f"b{j}_beta"])
+        out = rb.sample(B, out=rb.new_batch(B, probs=True, upperbounds=True), upperbounds_in=ub)
+        o = {k: v.cpu().numpy() for k, v in out.items()}
+        assert np.array_equal(o["indices"], z[f"b{j}_indices"])
+        assert np.array_equal(o["upperbounds"], z["upperbounds"])
+        assert np.array_equal(o["observations"], z[f"b{j}_obs"].astype(f32))
+        assert np.array_equal(o["next_observations"], z[f"b{j}_next_obs"].astype(f32))
+        assert np.array_equal(o["actions"].ravel(), z[f"b{j}_actions"])
+        assert np.array_equal(o["rewards"].ravel(), z[f"b{j}_rewards"])
+        assert np.array_equal(o["dones"].ravel() != 0, z[f"b{j}_dones"])
+        assert np.array_equal(o["probs"], z[f"b{j}_probs"])  # bitwise
+        check_elementwise(o["weights"].ravel(), z[f"b{j}_weights"], z[f"b{j}_weights64"], "weights")
+        assert float(rb.beta_dev) == f32(rb.beta)
+    assert int(rb.counter) == 2
+
+
+def filled(dev, capacity, n_adds, seed, n_step=1, obs_shape=(4,)):
+    """(device buffer, oracle) after the same `n_adds` random adds."""
+    rng = np.random.default_rng(seed)
+    rb = make(dev, capacity, obs_shape, n_step=n_step, seed=seed)
+    orc = PerOracle(capacity, obs_shape, n_step, 0.99, 0.5)
+    obs = rng.integers(0, 256, (n_adds + 1,) + obs_shape).astype(np.uint8)
+    rew = rng.choice(np.array([-1, 0, 0, 1, 0.5], f32), n_adds)
+    done = rng.random(n_adds) < 0.05
+    act = rng.integers(0, 6, n_adds)
+    for t in range(n_adds):
+        dev_add(rb, obs[t], act[t], rew[t], obs[t + 1], done[t])
+        orc.add(obs[t], act[t], rew[t], obs[t + 1], done[t])
+    return rb, orc, rng
+
+
+def update_both(rb, orc, idx, loss, leaf64):
+    rb.update_priorities(torch.from_numpy(idx).to(rb.device), torch.from_numpy(loss).to(rb.device))
+    orc.update_priorities(idx, loss)
+    for i, x in zip(idx, loss):
+        leaf64[i] = (abs(float(x)) + orc.eps) ** orc.alpha
+
+
+def check_sample(rb, orc, B, leaf_check=True):
+    """One device sample with its own draws against the oracle on the DOWNLOADED tree."""
+    out = rb.sample(B, out=rb.new_batch(B, probs=True, upperbounds=True))
+    o = {k: v.cpu().numpy() for k, v in out.items()}
+    tree, C, size = rb.tree.cpu().numpy(), rb.capacity, int(rb.state[1])
+    lo, hi = strata(tree[0], B)
+    ub = o["upperbounds"]
+    assert ((ub >= lo) & (ub < hi)).all()  # each draw in its stratum
+    idx = np.array([retrieve(tree, C, u) for u in ub])
+    assert np.array_equal(o["indices"], idx)
+    assert ((idx >= 0) & (idx < C)).all()
+    probs, w32 = per_weights(tree, C, size, idx, rb.beta)
+    _, w64 = per_weights(tree.astype(np.float64), C, size, idx, rb.beta, np.float64)
+    assert np.array_equal(o["probs"], probs)
+    check_elementwise(o["weights"].ravel(), w32, w64, "weights")
+    assert np.array_equal(o["observations"], orc.obs[idx].astype(f32))
+    assert np.array_equal(o["next_observations"], orc.next_obs[idx].astype(f32))
+    assert np.array_equal(o["rewards"].ravel(), orc.rewards[idx])
+    assert np.array_equal(o["actions"].ravel(), orc.actions[idx])
+    return o
+
+
+@pytest.mark.parametrize("B", [1, 8, 32])
+def test_sample_own_draws(dev, B):
+    C = 50  # not a power of two: leaves at two depths
+    rb, orc, rng = filled(dev, C, 70, seed=3)
+    leaf64 = np.zeros(C)
+    update_both(rb, orc, rng.integers(0, C, 40), rng.standard_normal(40).astype(f32), leaf64)
+    twin, _, _ = filled(dev, C, 70, seed=3)
+    twin.tree.copy_(rb.tree)
+    a = check_sample(rb, orc, B)
+    b = twin.sample(B, out=twin.new_batch(B, probs=True, upperbounds=True))
+    for k in a:  # same seed, same counter: the same draws, bitwise
+        assert np.array_equal(a[k], b[k].cpu().numpy()), k
+    c = check_sample(rb, orc, B)
+    assert not np.array_equal(a["upperbounds"], c["upperbounds"])  # the counter moved
+    assert int(rb.counter) == 2
+
+
+def test_capacity_one_million(dev):
+    """Depth 20 with both leaf depths in use: adds, updates scattered over the whole index range
+    (the widest levels are touched, B = 1024 per launch), then a sample."""
+    C = 1_000_000
+    rb, orc, rng = filled(dev, C, 2500, seed=5, n_step=3)
+    d = download(rb)
+    assert (d["pos"], d["size"]) == (orc.pos, orc.size) and orc.size > 2000
+    for key in ("obs", "next_obs", "actions", "rewards", "dones"):
+        assert np.array_equal(d[key][:orc.size + 1], getattr(orc, key)[:orc.size + 1]), key
+    assert np.array_equal(d["tree"], orc.tree)  # max_priority is 1: exactly 1 per leaf
+    leaf64 = (orc.leaves() != 0).astype(np.float64)
+    for n in (1024, 1024, 700, 33):
+        idx = rng.integers(0, C, n)
+        idx[:8] = [0, C - 1, C // 2, 48575, 48576, 48577, orc.size - 1, 0]  # edges + a duplicate
+        update_both(rb, orc, idx, (rng.standard_normal(n) * 2).astype(f32), leaf64)
+    d = download(rb)
+    assert bits(d["max_priority"]) == bits(orc.max_priority)
+    check_tree(d["tree"], C, orc.tree, leaf64, "1M")
+    depth = np.floor(np.log2(np.arange(C - 1, 2 * C - 1) + 1)).astype(int)
+    assert set(depth) == {19, 20}
+    for B in (32, 1024):
+        check_sample(rb, orc, B)
+
+
+def test_add_sample_update_replay_from_one_graph(dev):
+    C, B = 37, 8
+    bufs = [filled(dev, C, 20, seed=9, n_step=2)[0] for _ in range(2)]
+    rng = np.random.default_rng(1)
+    obs = torch.from_numpy(rng.integers(0, 256, (1, 4)).astype(np.uint8)).to(dev)
+    nxt = torch.from_numpy(rng.integers(0, 256, (1, 4)).astype(np.uint8)).to(dev)
+    act = torch.tensor([3], device=dev)
+    rew, done = torch.tensor([0.5], device=dev), torch.tensor([0.0], device=dev)
+    step = torch.zeros(1, dtype=torch.int64, device=dev)
+    outs = [rb.new_batch(B, probs=True, upperbounds=True) for rb in bufs]
+    for rb in bufs:
+        rb.total_timesteps = 10.0
+
+    def round_(rb, out):
+        rb.add(obs, nxt, act, rew, done)
+        rb.sample(B, out=out, step=step, step_offset=2)
+        rb.update_priorities(out["indices"], out["rewards"].view(-1) + out["weights"].view(-1))
+
+    for _ in range(3):
+        round_(bufs[0], outs[0])
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        round_(bufs[1], outs[1])
+    for _ in range(3):
+        g.replay()
+    torch.cuda.synchronize()
+    a, b = bufs
+    for k in ("obs", "next_obs", "actions", "rewards", "dones", "tree", "state", "ring_obs",
+              "ring_next_obs", "ring_actions", "ring_rewards", "ring_dones", "counter", "beta_dev"):
+        assert torch.equal(getattr(a, k), getattr(b, k)), k
+    for k in outs[0]:
+        assert torch.equal(outs[0][k], outs[1][k]), k
+    assert int(a.counter) == 3 and int(a.state[1]) > 3
+    assert float(a.beta_dev) == pytest.approx(0.4 + 2 * 0.6 / 10, rel=1e-6)
+
+
+def test_bad_arguments(dev):
+    from oc_cleanrl_amd import ops
+
+    with pytest.raises(ValueError):
+        make(torch.device("cpu"), 8, (4,))
+    with pytest.raises(ValueError):
+        make(dev, 8, (4,), num_envs=2)
+    with pytest.raises(ValueError):
+        make(dev, 8, (4,), n_step=9)
+    rb = make(dev, 8, (4,))
+    u8 = torch.zeros((1, 4), dtype=torch.uint8)
+    one = torch.zeros(1, device=dev)
+    with pytest.raises(ValueError):
+        rb.add(u8, u8.to(dev), torch.zeros(1, dtype=torch.int64, device=dev), one, one)
+    with pytest.raises(ValueError):
+        rb.sample(ops.PER_MAX_BATCH + 1)
+    with pytest.raises(ValueError):
+        rb.update_priorities(torch.zeros(4, dtype=torch.int64), torch.zeros(4, device=dev))
+    assert F32_FLOOR > 0
