@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCPPO_ABI_VERSION 30
+#define OCPPO_ABI_VERSION 31
 
 /* status codes */
 #define OCPPO_OK 0
@@ -1123,6 +1123,24 @@ OCPPO_API int ocppo_store_linear2(ocppo_stream_t stream, const float* frame, con
                                   double* ret_state, double* rms_state, const float* w1,
                                   const float* b1, const float* w2, const float* b2, float* y,
                                   int64_t ldy, int64_t N1, int64_t N2);
+/* ocppo_policy_head_env_step (noise read, H = 256 or 512, object frames) followed by
+ * ocppo_store_linear2 of the frames / rewards / dones it produced, in ONE launch: the rollout's
+ * [head + env step of step t-1, store into slot t, first two encoder layers of step t]. Every
+ * workgroup that needs env row n's action and frame recomputes them (the head is A+1 dots of H
+ * per row); one owner workgroup per 16 rows writes action_out / logprob_out / value_out, the env
+ * outputs frame_out [N, D] / env_reward_out / env_done_out [N] / ep_state [N, 5] (in place; read
+ * by the owner alone) and the store's outputs. No buffer is both read and written by different
+ * workgroups. Every output is bitwise what the two calls give. N <= 4096. */
+OCPPO_API int ocppo_head_env_store_linear2(
+    ocppo_stream_t stream, const float* hidden, int64_t H, const float* w_actor,
+    const float* b_actor, const float* w_critic, const float* b_critic, const float* noise,
+    int64_t A, int64_t* action_out, float* logprob_out, float* value_out, uint64_t seed,
+    const int64_t* step_base, int64_t step_offset, float* frame_out, float* env_reward_out,
+    float* env_done_out, float* ep_state, int64_t N, int64_t W, int64_t D, const void* prev_obs,
+    void* obs_out, int obs_dtype, float* net_obs, float* reward_out, float* done_out, int vecnorm,
+    double gamma, double epsilon, double clip_reward, double* ret_state, double* rms_state,
+    const float* w1, const float* b1, const float* w2, const float* b2, float* y, int64_t ldy,
+    int64_t N1, int64_t N2);
 
 /* ---------------------------------------------------------------------------------------------
  * CartPole-v1 vector env (config 1: cleanrl/ppo.py:81-91, 162 -- SyncVectorEnv of

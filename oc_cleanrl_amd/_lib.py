@@ -22,7 +22,7 @@ LIB_PATH = Path(os.environ.get("OCPPO_LIB", PKG / "lib" / "libocppo_hip.so"))
 HEADER = PKG.parent / "include" / "ocppo.h"
 
 # constants mirrored from include/ocppo.h (checked against the header by tests/test_abi.py)
-OCPPO_ABI_VERSION = 30
+OCPPO_ABI_VERSION = 31
 OCPPO_OK, OCPPO_E_INVALID, OCPPO_E_LAUNCH, OCPPO_E_WORKSPACE = 0, 1, 2, 3
 OCPPO_F32, OCPPO_BF16, OCPPO_U8 = 0, 1, 2
 OCPPO_X6_MBITS_ROWS = 2
@@ -140,6 +140,9 @@ SIGNATURES: dict[str, tuple[type, list]] = {
     "ocppo_minibatch_prepare_records": (I, [P, P, I64, I64, P, P, P, P, P, P, P]),
     "ocppo_store_linear2": (I, [P, P, P, P, I64, I64, I64, P, P, I, P, P, P, I, D, D, D, P, P, P,
                                 P, P, P, P, I64, I64, I64]),
+    "ocppo_head_env_store_linear2": (I, [P, P, I64, P, P, P, P, P, I64, P, P, P, U64, P, I64, P, P,
+                                         P, P, I64, I64, I64, P, P, I, P, P, P, I, D, D, D, P, P,
+                                         P, P, P, P, P, I64, I64, I64]),
 }
 
 

@@ -634,7 +634,8 @@ template <int S, bool RELU1, bool RELU2, int XDT>
 __device__ __forceinline__ void linear2_tile(
     int b, float* smem, const float* __restrict__ x, int64_t ldx, const float* __restrict__ w1,
     const float* __restrict__ b1, const float* __restrict__ w2, const float* __restrict__ b2,
-    float* __restrict__ y, int64_t ldy, int M, int N1, int N2, int K1, int ntm, int tiles) {
+    float* __restrict__ y, int64_t ldy, int M, int N1, int N2, int K1, int ntm, int tiles,
+    int xrow0 = 0) {
   const int ldh = N1 + 4;
   float* h1 = smem;                                                    // [16][ldh]
   floatx4* red = reinterpret_cast<floatx4*>(smem + 16 * ldh);          // [S-1][64]
@@ -646,7 +647,7 @@ __device__ __forceinline__ void linear2_tile(
   const int g = lane >> 4, c16 = lane & 15;
   const int row = tm * 16 + c16;
   const bool rok = row < M;
-  const float* xr = x + static_cast<int64_t>(rok ? row : 0) * ldx;
+  const float* xr = x + static_cast<int64_t>(rok ? row - xrow0 : 0) * ldx;  // x row 0 = row xrow0
 
   // every global operand of both phases is loaded up front (one round trip of latency): the x
   // chunks, this wave's W1 rows (phase-1 tiles ct = wv, wv + S, ...) and its W2 K-chunks
@@ -914,4 +915,274 @@ extern "C" int ocppo_store_linear2(ocppo_stream_t stream, const float* frame, co
     else launch_store_linear2<OCPPO_F32, false>(s, a);
   }
   return check_launch("ocppo_store_linear2");
+}
+
+// ---- policy head + env step of step t-1, its store, and step t's first two encoder layers --------
+// ocppo_policy_head_env_step followed by ocppo_store_linear2 in ONE launch. That seam of the
+// rollout chain is per env row: row n's action, next frame and stored slot depend only on row n of
+// the decoder output, the shared (A+1) x H head weights, row n of the Exp(1) noise and env n's
+// key. So, like the first encoder layer above, the head and the env step are recomputed by every
+// workgroup that needs them instead of waiting for a launch of their own:
+//   * workgroups [0, lin): the linear2 tiles; each recomputes the heads, the sample and the env
+//     frame of its 16 rows into LDS (head_env_rows) and takes its x operand from there;
+//   * workgroup lin (VecNormalize only): rewards and dones are functions of the env key alone
+//     (synth_env_reward_done), recomputed for all N envs into LDS, then vecnorm_block;
+//   * workgroups lin(+1) + tm: the OWNER of rows [16 tm, 16 tm + 16): the only writer of those
+//     rows' action / log-prob / value, env outputs (frame, reward, done, episode counters) and
+//     stored slot (store_rows_lds). The episode counters are read by their owner alone, so they
+//     are updated in place; everything other workgroups read (hidden, weights, noise, step_base,
+//     the previous slot) is read-only in this launch.
+// The head arithmetic is policy_head_fast_kernel's (head_load_row / head_dots / head_tail on the
+// same values in the same order), the env's is ocppo_synth_env.h's, the store's store_groups':
+// every output is bitwise what the two launches produce.
+#include "ocppo_categorical.h"
+#include "ocppo_synth_env.h"
+
+namespace ocppo {
+
+struct HeadEnvArgs {
+  const float* hidden;  // [N, 256 CH] decoder output of step t-1
+  const float* wa;
+  const float* ba;
+  const float* wc;
+  const float* bc;
+  const float* noise;   // [N, A] Exp(1)
+  int A;
+  int64_t* action_out;
+  float* logprob_out;
+  float* value_out;
+  uint64_t seed;
+  const int64_t* step_base;
+  int64_t step_offset;
+  float* frame;         // env outputs, written by the owner
+  float* reward;
+  float* done;
+  float* ep;            // [N, 5] or NULL
+};
+
+struct HeadEnvRows {  // one 16-row tile's env step, in LDS
+  float frame[16 * kLin2MaxK1];  // [16][D]
+  float logit[16][9];            // A logits, value in column 7 (+ pad)
+  float reward[16];
+  float done[16];
+};
+
+// Heads + sample + env step of rows [row0, row0 + 16) by the whole workgroup (256 threads): wave
+// wv does the A+1 dots of rows 4 wv .. 4 wv + 3 (weights in registers, as policy_head_fast_kernel),
+// all threads hash the action-free frame elements meanwhile, then lane r of wave 0 runs row r's
+// categorical tail (one wave64 pass for the 16 rows) and applies its action to frame element 1.
+// owner: also write the rows' outputs to memory.
+template <int CH>
+__device__ __forceinline__ void head_env_rows(const HeadEnvArgs& h, int row0, int N, int D,
+                                              bool owner, HeadEnvRows& s) {
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
+  const int A = h.A;
+  const int jo = lane >> 3;
+  const float bias = jo < A ? h.ba[jo] : (jo == 7 ? h.bc[0] : 0.f);
+  float4 w[8][CH];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float* wrow = j == 7 ? h.wc : h.wa + j * (256 * CH);
+#pragma unroll
+    for (int c = 0; c < CH; ++c)
+      w[j][c] = (j < A || j == 7) ? reinterpret_cast<const float4*>(wrow)[c * kWave + lane]
+                                  : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  float4 x[4][CH];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int row = row0 + 4 * wv + q;
+    if (row < N) {
+      head_load_row<CH>(h.hidden, row, lane, x[q]);
+    } else {
+#pragma unroll
+      for (int c = 0; c < CH; ++c) x[q][c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+  const int64_t trow = row0 + lane;  // the tail's row of this lane
+  const bool tl = wv == 0 && lane < 16 && trow < N;
+  float nzj[7];
+#pragma unroll
+  for (int j = 0; j < 7; ++j) nzj[j] = (tl && j < A) ? h.noise[trow * A + j] : 1.f;
+  const uint64_t step = static_cast<uint64_t>(h.step_base[0] + h.step_offset);
+  // frame elements other than 1 do not depend on the action: hashed while the loads are in flight
+  for (int e = tid; e < 16 * D; e += blockDim.x) {
+    const int r = e / D, k = e - r * D;
+    if (row0 + r < N && k != 1)
+      s.frame[e] = synth_env_obj(synth_env_key(h.seed, step, row0 + r), k, 0);
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const float t = head_dots<CH>(x[q], w, lane) + bias;
+    if ((lane & 7) == 0) s.logit[4 * wv + q][jo] = t;
+  }
+  __syncthreads();
+  if (tl) {
+    float l[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) l[j] = s.logit[lane][j];
+    const uint64_t key = synth_env_key(h.seed, step, trow);
+    const int best = head_tail(l, nzj, A, trow, h.action_out, h.logprob_out, nullptr, h.value_out,
+                               nullptr, owner);
+    if (D > 1) s.frame[lane * D + 1] = synth_env_obj(key, 1, best);
+    float r, d;
+    synth_env_reward_done(key, r, d);
+    s.reward[lane] = r;
+    s.done[lane] = d;
+    if (owner) synth_env_outcome(key, trow, h.reward, h.done, h.ep);
+  }
+  __syncthreads();
+  if (owner) {
+    for (int e = tid; e < 16 * D; e += blockDim.x)
+      if (row0 + e / D < N) h.frame[static_cast<int64_t>(row0) * D + e] = s.frame[e];
+  }
+}
+
+// store_groups for rows [row0, row0 + nrows) with the env outputs in LDS (f32 frames)
+template <int ODT, int VEC>
+__device__ __forceinline__ void store_rows_lds(const HeadEnvRows& s, int row0, int nrows, int W,
+                                               int D, const void* __restrict__ prev,
+                                               void* __restrict__ out, float* __restrict__ net,
+                                               float* __restrict__ reward_out,
+                                               float* __restrict__ done_out) {
+  const int DG = D / VEC;
+  const int groups = nrows * W * DG;
+  for (int g = threadIdx.x; g < groups; g += blockDim.x) {
+    const int r = g / (W * DG);
+    const int rem = g - r * W * DG;
+    const int w = rem / DG;
+    const int k = (rem - w * DG) * VEC;
+    const int64_t n = row0 + r;
+    float v[VEC];
+    if (w == W - 1 || s.done[r] != 0.f) {
+#pragma unroll
+      for (int q = 0; q < VEC; ++q) v[q] = s.frame[r * D + k + q];
+    } else {
+      VecIO<ODT, VEC>::load(prev, (n * W + w + 1) * D + k, v);
+    }
+    const int64_t o = (n * W + w) * D + k;
+    VecIO<ODT, VEC>::store(out, o, v);
+    if (net) {  // the network sees exactly what the rollout buffer holds
+      float back[VEC];
+#pragma unroll
+      for (int q = 0; q < VEC; ++q) back[q] = Elem<ODT>::roundtrip(v[q]);
+      VecIO<OCPPO_F32, VEC>::store(net, o, back);
+    }
+  }
+  if (static_cast<int>(threadIdx.x) < nrows) {
+    const int64_t n = row0 + threadIdx.x;
+    if (reward_out) reward_out[n] = s.reward[threadIdx.x];
+    if (done_out) done_out[n] = s.done[threadIdx.x];
+  }
+}
+
+template <int ODT, int VEC, bool VN, int CH>
+__global__ __launch_bounds__(256) void head_env_store_linear2_kernel(HeadEnvArgs h,
+                                                                     StoreLin2Args a) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  __shared__ HeadEnvRows rows;
+  const int b = blockIdx.x;
+  const int N = static_cast<int>(a.N), D = static_cast<int>(a.D);
+  if (b < a.lin_blocks) {
+    const int per_xcd = (a.tiles + 7) / 8;
+    const int t = (b % 8) * per_xcd + b / 8;  // linear2_tile's tile order
+    if (t >= a.tiles) return;
+    const int tm = t % a.ntm;
+    head_env_rows<CH>(h, tm * 16, N, D, false, rows);
+    linear2_tile<4, true, true, ODT>(b, smem, rows.frame, a.D, a.w1, a.b1, a.w2, a.b2, a.y, a.ldy,
+                                     N, a.N1, a.N2, D, a.ntm, a.tiles, tm * 16);
+    return;
+  }
+  if (VN && b == a.lin_blocks) {
+    const uint64_t step = static_cast<uint64_t>(h.step_base[0] + h.step_offset);
+    for (int n = threadIdx.x; n < N; n += blockDim.x)
+      synth_env_reward_done(synth_env_key(h.seed, step, n), smem[n], smem[N + n]);
+    __syncthreads();
+    vecnorm_block(smem, smem + N, a.N, a.gamma, a.eps, a.clip, a.ret, a.rms, a.reward_out);
+    return;
+  }
+  const int row0 = (b - a.lin_blocks - (VN ? 1 : 0)) * 16;
+  head_env_rows<CH>(h, row0, N, D, true, rows);
+  store_rows_lds<ODT, VEC>(rows, row0, N - row0 < 16 ? N - row0 : 16, a.W, D, a.prev, a.out, a.net,
+                           VN ? nullptr : a.reward_out, a.done_out);
+}
+
+template <int ODT, bool VN, int CH>
+static void launch_head_env_store_linear2(hipStream_t s, const HeadEnvArgs& h,
+                                          const StoreLin2Args& a) {
+  size_t lds = sizeof(float) * 16 * (a.N1 + 4) + sizeof(floatx4) * 64 * 3;
+  if (VN && lds < sizeof(float) * 2 * a.N) lds = sizeof(float) * 2 * a.N;
+  const dim3 grid(a.lin_blocks + (VN ? 1 : 0) + a.ntm);
+  if (a.D % 4 == 0)
+    hipLaunchKernelGGL((head_env_store_linear2_kernel<ODT, 4, VN, CH>), grid, dim3(256), lds, s, h,
+                       a);
+  else
+    hipLaunchKernelGGL((head_env_store_linear2_kernel<ODT, 1, VN, CH>), grid, dim3(256), lds, s, h,
+                       a);
+}
+
+template <int CH>
+static void launch_head_env_store_linear2_dt(hipStream_t s, int obs_dtype, bool vn,
+                                             const HeadEnvArgs& h, const StoreLin2Args& a) {
+  if (obs_dtype == OCPPO_BF16) {
+    if (vn) launch_head_env_store_linear2<OCPPO_BF16, true, CH>(s, h, a);
+    else launch_head_env_store_linear2<OCPPO_BF16, false, CH>(s, h, a);
+  } else {
+    if (vn) launch_head_env_store_linear2<OCPPO_F32, true, CH>(s, h, a);
+    else launch_head_env_store_linear2<OCPPO_F32, false, CH>(s, h, a);
+  }
+}
+
+}  // namespace ocppo
+
+extern "C" int ocppo_head_env_store_linear2(
+    ocppo_stream_t stream, const float* hidden, int64_t H, const float* w_actor,
+    const float* b_actor, const float* w_critic, const float* b_critic, const float* noise,
+    int64_t A, int64_t* action_out, float* logprob_out, float* value_out, uint64_t seed,
+    const int64_t* step_base, int64_t step_offset, float* frame_out, float* env_reward_out,
+    float* env_done_out, float* ep_state, int64_t N, int64_t W, int64_t D, const void* prev_obs,
+    void* obs_out, int obs_dtype, float* net_obs, float* reward_out, float* done_out, int vecnorm,
+    double gamma, double epsilon, double clip_reward, double* ret_state, double* rms_state,
+    const float* w1, const float* b1, const float* w2, const float* b2, float* y, int64_t ldy,
+    int64_t N1, int64_t N2) {
+  const char* const fn = "ocppo_head_env_store_linear2";
+  OCPPO_REQUIRE(N >= 1 && N <= 4096 && W >= 1 && W <= 64 && D >= 1 && D <= kLin2MaxK1 &&
+                    N1 >= 16 && N1 % 16 == 0 && N1 <= kLin2MaxN1 && N2 >= 1 && N2 <= INT32_MAX &&
+                    ldy >= N2 && (H == 256 || H == 512) && A >= 1 && A <= 7,
+                "%s: bad sizes N=%lld W=%lld D=%lld N1=%lld N2=%lld H=%lld A=%lld (N <= 4096, "
+                "D <= 64, N1 %% 16 == 0, N1 <= 512, H 256 or 512, A <= 7)", fn, (long long)N,
+                (long long)W, (long long)D, (long long)N1, (long long)N2, (long long)H,
+                (long long)A);
+  OCPPO_REQUIRE(obs_dtype == OCPPO_F32 || obs_dtype == OCPPO_BF16,
+                "%s: obs dtype must be OCPPO_F32 or OCPPO_BF16 (object vectors)", fn);
+  OCPPO_REQUIRE(hidden && w_actor && b_actor && w_critic && b_critic && noise && action_out &&
+                    logprob_out && value_out && step_base && frame_out && env_reward_out &&
+                    env_done_out && prev_obs && obs_out && reward_out && w1 && w2 && y,
+                "%s: null pointer", fn);
+  OCPPO_REQUIRE(prev_obs != obs_out, "%s: prev_obs must not alias obs_out", fn);
+  OCPPO_REQUIRE(!vecnorm || (ret_state && rms_state && reward_out != env_reward_out),
+                "%s: VecNormalize needs ret/rms state and a separate reward_out", fn);
+  OCPPO_REQUIRE(((reinterpret_cast<uintptr_t>(hidden) | reinterpret_cast<uintptr_t>(w_actor) |
+                  reinterpret_cast<uintptr_t>(w_critic) | reinterpret_cast<uintptr_t>(w2)) & 15) == 0,
+                "%s: hidden, head weights and w2 must be 16-B aligned", fn);
+  HeadEnvArgs h;
+  h.hidden = hidden; h.wa = w_actor; h.ba = b_actor; h.wc = w_critic; h.bc = b_critic;
+  h.noise = noise; h.A = (int)A; h.action_out = action_out; h.logprob_out = logprob_out;
+  h.value_out = value_out; h.seed = seed; h.step_base = step_base; h.step_offset = step_offset;
+  h.frame = frame_out; h.reward = env_reward_out; h.done = env_done_out; h.ep = ep_state;
+  StoreLin2Args a;
+  a.frame = nullptr; a.reward = nullptr; a.done = nullptr; a.N = N; a.D = D; a.W = (int)W;
+  a.prev = prev_obs; a.out = obs_out; a.net = net_obs; a.reward_out = reward_out;
+  a.done_out = done_out; a.gamma = gamma; a.eps = epsilon; a.clip = clip_reward;
+  a.ret = ret_state; a.rms = rms_state;
+  a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.y = y; a.ldy = ldy;
+  a.N1 = (int)N1; a.N2 = (int)N2;
+  a.ntm = (int)((N + 15) / 16);
+  a.tiles = a.ntm * (int)((N2 + 15) / 16);
+  a.lin_blocks = 8 * ((a.tiles + 7) / 8);
+  clear_stale_error();
+  hipStream_t s = as_stream(stream);
+  if (H == 256) launch_head_env_store_linear2_dt<1>(s, obs_dtype, vecnorm != 0, h, a);
+  else launch_head_env_store_linear2_dt<2>(s, obs_dtype, vecnorm != 0, h, a);
+  return check_launch(fn);
 }

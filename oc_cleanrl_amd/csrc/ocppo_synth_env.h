@@ -48,15 +48,22 @@ __device__ __forceinline__ uint8_t synth_env_pixel(uint64_t key, int64_t k, int6
   return static_cast<uint8_t>(v);
 }
 
+// reward / done of the env with key `key`: functions of the key alone (no action, no state), so
+// any workgroup can recompute them
+__device__ __forceinline__ void synth_env_reward_done(uint64_t key, float& r, float& d) {
+  const float ur = unit24(splitmix64(key ^ 0x5DEECE66Dull));
+  r = ur < 0.005f ? 1.f : (ur < 0.01f ? -1.f : 0.f);
+  const float ud = unit24(splitmix64(key ^ 0xB5297A4Dull));
+  d = ud < (1.0f / 3500.0f) ? 1.f : 0.f;
+}
+
 // reward / done of env n and its RecordEpisodeStatistics counters (one thread per env)
 __device__ __forceinline__ void synth_env_outcome(uint64_t key, int64_t n,
                                                   float* __restrict__ reward_out,
                                                   float* __restrict__ done_out,
                                                   float* __restrict__ ep) {
-  const float ur = unit24(splitmix64(key ^ 0x5DEECE66Dull));
-  const float r = ur < 0.005f ? 1.f : (ur < 0.01f ? -1.f : 0.f);
-  const float ud = unit24(splitmix64(key ^ 0xB5297A4Dull));
-  const float d = ud < (1.0f / 3500.0f) ? 1.f : 0.f;
+  float r, d;
+  synth_env_reward_done(key, r, d);
   reward_out[n] = r;
   done_out[n] = d;
   if (ep) {

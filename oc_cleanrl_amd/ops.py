@@ -1323,6 +1323,59 @@ def store_linear2(frame, reward, done, prev_obs, obs_out, net_obs, done_out, rew
     return y
 
 
+def head_env_store_linear2_ok(hidden, w_actor, w_critic, env) -> bool:
+    """head_env_store_linear2 applies: policy_head_env_step's conditions with H = 256 or 512."""
+    return policy_head_env_ok(hidden, w_actor, w_critic, env) and hidden.shape[1] in (256, 512) \
+        and env.frame.shape[1] <= 64
+
+
+def head_env_store_linear2(hidden, w_actor, b_actor, w_critic, b_critic, noise, action_out,
+                           logprob_out, value_out, env, step_offset: int, prev_obs, obs_out,
+                           net_obs, done_out, reward_out, w1, b1, w2, b2, y, vecnorm_state=None,
+                           gamma=0.99, epsilon=1e-8, clip_reward=10.0):
+    """ONE launch: policy_head_env_step(hidden, ..., env, step_offset) followed by
+    store_linear2(env.frame, env.reward, env.done, prev_obs, obs_out, ...) -- the head, sample
+    and env step of one rollout step, its store, and the next step's first two encoder layers
+    (ocppo_head_env_store_linear2; bitwise the two launches). noise [N, A] is read."""
+    N, H = hidden.shape
+    A = w_actor.shape[0]
+    D = env.frame.shape[1]
+    W = obs_out.shape[1]
+    dev = hidden.device
+    f = torch.float32
+    if tuple(w_actor.shape) != (A, H) or w_critic.numel() != H or b_actor.numel() != A:
+        raise ValueError("head weights do not match hidden")
+    if prev_obs.shape != obs_out.shape or prev_obs.dtype != obs_out.dtype or \
+            tuple(obs_out.shape) != (N, W, D) or obs_out.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"obs slots must be [N, W, D] f32|bf16, got {tuple(obs_out.shape)} "
+                         f"{obs_out.dtype}")
+    N1, N2 = w1.shape[0], w2.shape[0]
+    if tuple(w1.shape) != (N1, D) or tuple(w2.shape) != (N2, N1) or y.shape[0] != N or \
+            y.shape[1] != N2 or y.stride(1) != 1 or y.dtype != f:
+        raise ValueError(f"shapes: frame {tuple(env.frame.shape)}, w1 {tuple(w1.shape)}, "
+                         f"w2 {tuple(w2.shape)}, y {tuple(y.shape)}")
+    vn = vecnorm_state is not None
+    ret, rms = vecnorm_state if vn else (None, None)
+    call("ocppo_head_env_store_linear2", _stream(dev), _check(hidden, "hidden", f, dev), H,
+         _check(w_actor, "w_actor", f, dev), _check(b_actor, "b_actor", f, dev, A),
+         _check(w_critic, "w_critic", f, dev, H), _check(b_critic, "b_critic", f, dev, 1),
+         _check(noise, "noise", f, dev, N * A), A,
+         _check(action_out, "action_out", torch.int64, dev, N),
+         _check(logprob_out, "logprob_out", f, dev, N), _check(value_out, "value_out", f, dev, N),
+         env.seed & 0xFFFFFFFFFFFFFFFF, _check(env.step_base, "step_base", torch.int64, dev, 1),
+         int(step_offset), _check(env.frame, "frame", f, dev, N * D),
+         _check(env.reward, "reward", f, dev, N), _check(env.done, "done", f, dev, N),
+         _opt(env.ep_state, "ep_state", f, dev, N * 5), N, W, D,
+         _check(prev_obs, "prev_obs", None, dev), _check(obs_out, "obs_out", None, dev),
+         _DTYPE_CODE[obs_out.dtype], _opt(net_obs, "net_obs", f, dev, N * W * D),
+         _check(reward_out, "reward_out", f, dev, N), _opt(done_out, "done_out", f, dev, N),
+         int(vn), float(gamma), float(epsilon), float(clip_reward),
+         _opt(ret, "ret_state", torch.float64, dev, N), _opt(rms, "rms_state", torch.float64, dev, 3),
+         _check(w1, "w1", f, dev), _opt(b1, "b1", f, dev, N1), _check(w2, "w2", f, dev),
+         _opt(b2, "b2", f, dev, N2), y.data_ptr(), y.stride(0) if N > 1 else N2, N1, N2)
+    return y
+
+
 # ---------------------------------------------------------------------------------------------
 # Linear(+ReLU) backward, elementwise part: threshold_backward + bias sum in one pass
 # (autograd of architectures/ppo.py:60-84 inside ppo_atari_oc.py:605)

@@ -56,6 +56,12 @@ def storage_dtype(args: Args, pixels: bool, integer_obs: bool = True) -> torch.d
 # The rollout's synthetic object-frame env step fused into the policy head's launch
 # (ops.policy_head_env_step: bitwise the two-launch step; one launch fewer per env step).
 FUSED_HEAD_ENV = True
+# ... and that head + env launch folded into the NEXT step's store + encoder launch
+# (ops.head_env_store_linear2: the seam is per env row, so every workgroup recomputes the rows it
+# needs): the rollout's order of a step is rotated to decoder -> [head, env, store, encoder layers
+# 1-2 of step t+1] -> middle layers -> cache layer, four launches per env step instead of five,
+# bitwise the same rollout (needs FUSED_HEAD_ENV; off: the five-launch chain)
+ROLLOUT_FUSED_STEP = True
 # The weights' bf16 planes for the next minibatch's GEMMs written by the optimizer step itself
 # (ops.FlatAdam.write_planes) instead of a split launch per minibatch. Off: at config 2 nearly
 # every parameter has planes (W^T ones among them, scattered 2-B writes from the Adam lanes) and
@@ -408,6 +414,12 @@ class PPOTrainer:
         # (physical slot (t-1) mod W) and the decoder's first layer reads the slots rotated by
         # t mod W (ocppo_linear_cache_ring / ocppo_linear_act_ring), bit-identical to the shift
         self.cache_ring = self.rollout_fusion and a.rollout_cache_ring and self._ring_decoder()
+        # ... and the head + env step of step t-1 ride in that launch too (ROLLOUT_FUSED_STEP)
+        self.fused_step_ok = (
+            self.rollout_fusion and not self.host_env and T >= 2 and
+            a.sampling_noise in ("kernel", "rollout") and ops.head_env_store_linear2_ok(
+                torch.empty((N, self.H), dtype=f32, device=dev), self.agent.actor.weight,
+                self.agent.critic.weight, self.env))
         self.ret_state = torch.zeros(N, dtype=torch.float64, device=dev)
         self.rms_state = torch.tensor([0.0, 1.0, 1e-4], dtype=torch.float64, device=dev)
 
@@ -647,16 +659,27 @@ class PPOTrainer:
             self.timer.bracket("frame_cache", lambda: ops.frame_cache_shift(
                 self.enc_cache, fresh, self.dones[t]))
 
-    def _store_encode(self, t: int):
+    def _store_encode(self, t: int, hidden=None):
         """Store of step t-1 + encode of step t's newest frame into the cache, in 2 + (encoder
-        depth - 3) launches (ops.store_linear2, middle layers, ops.linear_cache_shift)."""
+        depth - 3) launches (ops.store_linear2, middle layers, ops.linear_cache_shift). hidden:
+        the decoder output of step t-1, whose policy head and env step have not run yet: they ride
+        in the first launch (ops.head_env_store_linear2)."""
         a, env, net = self.args, self.env, self.agent.network
+        ag = self.agent
         lins = [m for m in net[:self.agent._flat] if isinstance(m, nn.Linear)]
         vn = (self.ret_state, self.rms_state) if a.vecnorm_reward else None
-        self.timer.bracket("store_encode", lambda: ops.store_linear2(
-            env.frame, env.reward, env.done, self.obs[t - 1], self.obs[t], self.net_obs,
-            self.dones[t], self.rewards[t - 1], lins[0].weight, lins[0].bias, lins[1].weight,
-            lins[1].bias, self.enc_pair, vecnorm_state=vn))
+        if hidden is not None:
+            self.timer.bracket("head_store_encode", lambda: ops.head_env_store_linear2(
+                hidden, ag.actor.weight, ag.actor.bias, ag.critic.weight, ag.critic.bias,
+                self.noise[t - 1], self.actions[t - 1], self.logprobs[t - 1], self.values[t - 1],
+                env, t - 1, self.obs[t - 1], self.obs[t], self.net_obs, self.dones[t],
+                self.rewards[t - 1], lins[0].weight, lins[0].bias, lins[1].weight, lins[1].bias,
+                self.enc_pair, vecnorm_state=vn))
+        else:
+            self.timer.bracket("store_encode", lambda: ops.store_linear2(
+                env.frame, env.reward, env.done, self.obs[t - 1], self.obs[t], self.net_obs,
+                self.dones[t], self.rewards[t - 1], lins[0].weight, lins[0].bias, lins[1].weight,
+                lins[1].bias, self.enc_pair, vecnorm_state=vn))
         x = self.enc_pair
         for i, lin in enumerate(lins[2:-1]):
             x = self.timer.bracket("encoder_mid" if i == 0 else f"encoder_mid{i}",
@@ -681,8 +704,9 @@ class PPOTrainer:
         if not self.rollout_fusion:  # else the store rides in step t+1's encoder launch
             self._store(t)
 
-    def _act(self, t: int, env_step: bool = False) -> bool:
-        """Actions / log-probs / values of step t; True when the env step ran too."""
+    def _act(self, t: int, env_step: bool = False, hidden=None) -> bool:
+        """Actions / log-probs / values of step t (hidden: its trunk output, when the caller has
+        it already); True when the env step ran too."""
         ag = self.agent
         if self.args.sampling_noise == "torch":
             # the reference's stream: one Exp(1) draw of [N, A] per step (Categorical.sample at
@@ -690,7 +714,8 @@ class PPOTrainer:
             self.noise[t].exponential_()
         px = self.exp_stream.philox(t) if self.args.sampling_noise == "head" else None
         if self.fused_head:
-            hidden = self._policy_hidden(t)
+            if hidden is None:
+                hidden = self._policy_hidden(t)
             if env_step and FUSED_HEAD_ENV and ops.policy_head_env_ok(
                     hidden, ag.actor.weight, ag.critic.weight, self.env):
                 self.timer.bracket("action_head_env", lambda: ops.policy_head_env_step(
@@ -768,8 +793,18 @@ class PPOTrainer:
         """Rollout (:500-530) + bootstrap + GAE (:533-547) + minibatch adv stats (:577-579)."""
         with torch.no_grad(), agents.rollout_inference():
             self._rollout_begin()
-            for t in range(self.T):
-                self._rollout_step(t)
+            if self.fused_step_ok and ROLLOUT_FUSED_STEP and FUSED_HEAD_ENV:
+                # a step's order rotated: the head + env step of step t-1 run in step t's store +
+                # encoder launch; the ends (step 0's encode, the last head) are the plain kernels
+                hidden = self._policy_hidden(0)
+                for t in range(1, self.T):
+                    self._store_encode(t, hidden)
+                    hidden = self._decode_cache(t)
+                ran = self._act(self.T - 1, env_step=True, hidden=hidden)
+                assert ran
+            else:
+                for t in range(self.T):
+                    self._rollout_step(t)
             self.env.advance(self.T)
             self._rollout_end()
 
