@@ -32,6 +32,32 @@ def layer_init(layer, std=np.sqrt(2), bias_const=0.0):
     return layer
 
 
+def object_trunk(obs_shape, encoder_dims, decoder_dims, init=lambda layer: layer):
+    """The object-vector trunk of architectures/ppo.py:60-84 as (module list, output width): a
+    per-frame Linear + ReLU encoder on the last (feature) dim, Flatten over the frame stack, a
+    Linear + ReLU decoder. `init` (layer_init) is applied to each Linear as it is made, so modules
+    are created and initialised in network order."""
+    layers, d = [], obs_shape[-1]
+    for l in encoder_dims:
+        layers += [init(nn.Linear(d, l)), nn.ReLU()]
+        d = l
+    layers.append(nn.Flatten())
+    d *= int(np.prod(obs_shape[:-1], dtype=int))
+    for l in decoder_dims:
+        layers += [init(nn.Linear(d, l)), nn.ReLU()]
+        d = l
+    return layers, d
+
+
+def nature_cnn(in_channels: int) -> list:
+    """The value-based learners' NatureCNN trunk (architectures/dqn.py:12-19, default PyTorch
+    init) up to the Flatten: 3136 features of an 84 x 84 input."""
+    return [nn.Conv2d(in_channels, 32, 8, stride=4), nn.ReLU(),
+            nn.Conv2d(32, 64, 4, stride=2), nn.ReLU(),
+            nn.Conv2d(64, 64, 3, stride=1), nn.ReLU(),
+            nn.Flatten()]
+
+
 class NormalizeImg(nn.Module):
     """x / 255 (architectures/common.py:19-22)."""
 
@@ -1285,23 +1311,11 @@ class PPObj(_ActorCritic):
     def __init__(self, envs, device=None, encoder_dims=(128, 64), decoder_dims=(32,)):
         super().__init__()
         self.device = device
-        dims = tuple(envs.observation_space.shape)
-        layers = nn.ModuleList()
-        in_dim = dims[-1]
-        for l in encoder_dims:
-            layers.append(layer_init(nn.Linear(in_dim, l)))
-            layers.append(nn.ReLU())
-            in_dim = l
-        layers.append(nn.Flatten())
-        in_dim *= int(np.prod(dims[:-1], dtype=int))
-        l = in_dim
-        for l in decoder_dims:
-            layers.append(layer_init(nn.Linear(in_dim, l)))
-            layers.append(nn.ReLU())
-            in_dim = l
+        layers, d = object_trunk(tuple(envs.observation_space.shape), encoder_dims, decoder_dims,
+                                 layer_init)
         self.network = nn.Sequential(*layers)
-        self.actor = layer_init(nn.Linear(l, envs.action_space.n), std=0.01)
-        self.critic = layer_init(nn.Linear(l, 1), std=1)
+        self.actor = layer_init(nn.Linear(d, envs.action_space.n), std=0.01)
+        self.critic = layer_init(nn.Linear(d, 1), std=1)
         self._flat = len(encoder_dims) * 2  # index of the Flatten in self.network
 
     # The encoder acts on each stacked frame alone (Linear on the last dim), so the rollout can

@@ -22,10 +22,7 @@ head.
 """
 from __future__ import annotations
 
-import json
-import time
-from dataclasses import asdict, dataclass
-from pathlib import Path
+from dataclasses import dataclass
 from typing import Optional
 
 import numpy as np
@@ -33,9 +30,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .agents import Predictor, fused_trunk, q_head
-from .args import OBS_MODES, parse_dataclass
-from .dqn import DQNTrainer
+from .agents import Predictor, fused_trunk, nature_cnn, object_trunk, q_head
+from .dqn import DQNTrainer, check_actions, check_atoms, learner_main, run_learner
 
 
 @dataclass
@@ -100,12 +96,8 @@ class QNetworkC51(Predictor):
         self.n_atoms = n_atoms
         self.register_buffer("atoms", torch.linspace(v_min, v_max, steps=n_atoms))
         self.n = n_actions
-        self.network = nn.Sequential(
-            nn.Conv2d(obs_shape[0], 32, 8, stride=4), nn.ReLU(),
-            nn.Conv2d(32, 64, 4, stride=2), nn.ReLU(),
-            nn.Conv2d(64, 64, 3, stride=1), nn.ReLU(),
-            nn.Flatten(), nn.Linear(3136, 512), nn.ReLU(),
-            nn.Linear(512, self.n * n_atoms))
+        self.network = nn.Sequential(*nature_cnn(obs_shape[0]), nn.Linear(3136, 512), nn.ReLU(),
+                                     nn.Linear(512, self.n * n_atoms))
 
     def _scale(self, x):
         return x / 255.0
@@ -153,17 +145,8 @@ class QNetworkC51Obj(QNetworkC51):
         self.n_atoms = n_atoms
         self.register_buffer("atoms", torch.linspace(v_min, v_max, steps=n_atoms))
         self.n = n_actions
-        layers, d = [], obs_shape[-1]
-        for l in encoder_dims:
-            layers += [nn.Linear(d, l), nn.ReLU()]
-            d = l
-        layers.append(nn.Flatten())
-        d *= int(np.prod(obs_shape[:-1]))
-        for l in decoder_dims:
-            layers += [nn.Linear(d, l), nn.ReLU()]
-            d = l
-        layers.append(nn.Linear(d, self.n * n_atoms))
-        self.network = nn.Sequential(*layers)
+        layers, d = object_trunk(obs_shape, encoder_dims, decoder_dims)
+        self.network = nn.Sequential(*layers, nn.Linear(d, self.n * n_atoms))
 
     def _scale(self, x):
         return x
@@ -182,11 +165,9 @@ class C51Trainer(DQNTrainer):
     network, acting rule, train step and hard target copy."""
 
     def __init__(self, args: C51Args, device, log: bool = True):
-        if not (2 <= args.n_atoms <= ops.C51_MAX_ATOMS):
-            raise ValueError(f"n_atoms={args.n_atoms}: need 2 <= n_atoms <= {ops.C51_MAX_ATOMS}")
+        check_atoms(args.n_atoms)
         super().__init__(args, device, log)
-        if self.A > ops.C51_MAX_ACTIONS:
-            raise ValueError(f"{self.A} actions: the C51 kernels take at most {ops.C51_MAX_ACTIONS}")
+        check_actions(self.A, "C51")
         self.fused_act = False  # DQN's Q-head launch does not apply: acting is self._act
         B = args.batch_size
         self.dlogits = torch.zeros((B, self.A * args.n_atoms), dtype=torch.float32,
@@ -226,48 +207,15 @@ class C51Trainer(DQNTrainer):
         constant)."""
         self.t_flat.copy_(self.opt.params)
 
-    def metrics(self) -> dict:
-        st = self.td_stats.tolist()
-        ep_ret, ep_len, ep_n = self.env.pop_episode_stats()
-        m = {"losses/loss": st[0], "losses/q_values": st[1],
-             "charts/epsilon": float(self.epsilon)}
-        if ep_n > 0:
-            m["charts/Episodic_Original_Reward"] = ep_ret / ep_n
-            m["charts/Episodic_Length"] = ep_len / ep_n
-        return m
+    LOSS_KEY = "losses/loss"
 
 
 def run_c51(args: C51Args, device=None) -> C51Trainer:
-    device = device or torch.device("cuda:0")
-    tr = C51Trainer(args, device)
-    run_name = f"{args.env_id}__{args.exp_name}__{args.seed}__{int(time.time())}".replace("/", "_")
-    run_dir = Path(args.log_dir) / run_name
-    run_dir.mkdir(parents=True, exist_ok=True)
-    (run_dir / "args.json").write_text(json.dumps(asdict(args), indent=1, default=str))
-    start = time.time()
-    chunk = max(args.train_frequency, args.log_every - args.log_every % args.train_frequency)
-    with open(run_dir / "metrics.jsonl", "w") as w:
-        while tr.global_step < args.total_timesteps:
-            n = min(chunk, args.total_timesteps - tr.global_step)
-            n -= n % args.train_frequency if tr._graphable() else 0
-            if n <= 0:
-                break
-            tr.steps(n)
-            m = tr.metrics()
-            m["charts/SPS"] = int(tr.global_step * args.num_envs / (time.time() - start))
-            m["global_step"] = tr.global_step
-            w.write(json.dumps(m) + "\n")
-    if args.save_model:
-        torch.save(tr.checkpoint(), run_dir / f"{args.exp_name}.cleanrl_model")
-    return tr
+    return run_learner(C51Trainer, args, device)
 
 
 def main(argv=None):
-    args = parse_dataclass(C51Args, argv, None, "oc_cleanrl_amd C51 (c51_atari_oc.py surface)")
-    if args.obs_mode not in OBS_MODES:
-        raise SystemExit(f"bad obs_mode {args.obs_mode}")
-    tr = run_c51(args)
-    print({k: round(v, 5) for k, v in tr.metrics().items()})
+    learner_main(C51Args, run_c51, "oc_cleanrl_amd C51 (c51_atari_oc.py surface)", argv)
 
 
 if __name__ == "__main__":

@@ -13,6 +13,7 @@
 // One thread per env; the state stays in HBM between launches, so a captured rollout graph
 // replays it step after step.
 #include "ocppo_common.h"
+#include "ocppo_rng.h"
 
 namespace ocppo {
 
@@ -29,22 +30,15 @@ constexpr double kXThreshold = 2.4;
 constexpr int64_t kMaxSteps = 500;
 }  // namespace cartpole
 
-__device__ __forceinline__ uint64_t cp_mix(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
 // uniform(-0.05, 0.05) as numpy computes low + (high - low) * u, u a 53-bit double in [0, 1)
 __device__ __forceinline__ void cartpole_reset_state(uint64_t seed, int64_t n, int64_t episode,
                                                      double* st) {
-  const uint64_t key = cp_mix(cp_mix(seed) + static_cast<uint64_t>(n) * 0x100000001B3ull) ^
-                       cp_mix(static_cast<uint64_t>(episode) + 0x632BE59BD9B4E019ull);
+  const uint64_t key = splitmix64(splitmix64(seed) + static_cast<uint64_t>(n) * 0x100000001B3ull) ^
+                       splitmix64(static_cast<uint64_t>(episode) + 0x632BE59BD9B4E019ull);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const uint64_t h = cp_mix(key + static_cast<uint64_t>(i));
-    const double u = static_cast<double>(h >> 11) * (1.0 / 9007199254740992.0);
+    const uint64_t h = splitmix64(key + static_cast<uint64_t>(i));
+    const double u = unit53(h);
     st[i] = -0.05 + (0.05 - -0.05) * u;
   }
 }

@@ -12,17 +12,11 @@
 // sampler is by distribution, the TD math is bit-level).
 #include "ocppo_common.h"
 #include "ocppo_categorical.h"
+#include "ocppo_rng.h"
 #include "ocppo_store.h"
 #include "ocppo_synth_env.h"
 
 namespace ocppo {
-
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
 
 template <int SDT, int ODT>
 __global__ __launch_bounds__(256) void replay_add_kernel(
@@ -71,9 +65,10 @@ __global__ __launch_bounds__(256) void replay_add_kernel(
 __device__ __forceinline__ void sample_index(uint64_t seed, int64_t ctr, int64_t b, int64_t pos,
                                              int64_t full, int64_t size, int64_t E, int64_t& i,
                                              int64_t& e) {
-  const uint64_t h = mix64(mix64(seed ^ 0xD1B54A32D192ED03ull) + static_cast<uint64_t>(ctr) * 0x100000001B3ull +
-                           static_cast<uint64_t>(b));
-  const uint64_t h2 = mix64(h);
+  const uint64_t h = splitmix64(splitmix64(seed ^ 0xD1B54A32D192ED03ull) +
+                                static_cast<uint64_t>(ctr) * 0x100000001B3ull +
+                                static_cast<uint64_t>(b));
+  const uint64_t h2 = splitmix64(h);
   if (full)
     i = (static_cast<int64_t>(h % static_cast<uint64_t>(size - 1)) + 1 + pos) % size;
   else
@@ -115,25 +110,18 @@ __global__ __launch_bounds__(256) void replay_sample_kernel(
 
 __global__ void counter_add_kernel(int64_t* counter, int64_t n) { counter[0] += n; }
 
-// epsilon-greedy (dqn_atari_oc.py:345-350): epsilon = max(slope * t + start_e, end_e) with
-// slope = (end_e - start_e) / duration (linear_schedule, :230-232, in double); ONE coin for all
-// envs; random actions uniform in [0, A), else argmax_j q[e, j] (first maximum, like torch).
+// epsilon-greedy (dqn_atari_oc.py:345-350): EpsGreedy's schedule, coin and random actions
+// (ocppo_rng.h), else argmax_j q[e, j] (first maximum, like torch).
 __global__ __launch_bounds__(256) void epsilon_greedy_kernel(
     const float* __restrict__ q, int64_t E, int A, uint64_t seed, const int64_t* __restrict__ step,
     int64_t step_offset, double start_e, double end_e, double duration,
     int64_t* __restrict__ actions, float* __restrict__ eps_out) {
-  const int64_t t = step[0] + step_offset;
-  const double slope = (end_e - start_e) / duration;
-  double eps = slope * static_cast<double>(t) + start_e;
-  eps = eps > end_e ? eps : end_e;
-  const uint64_t h = mix64(mix64(seed ^ 0xA0761D6478BD642Full) + static_cast<uint64_t>(t));
-  const double coin = static_cast<double>(h >> 11) * (1.0 / 9007199254740992.0);  // [0, 1)
-  const bool explore = coin < eps;
+  const EpsGreedy eg(seed, step[0] + step_offset, start_e, end_e, duration);
   for (int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < E;
        e += static_cast<int64_t>(gridDim.x) * blockDim.x) {
     int64_t a;
-    if (explore) {
-      a = static_cast<int64_t>(mix64(h + static_cast<uint64_t>(e) + 1) % static_cast<uint64_t>(A));
+    if (eg.explore) {
+      a = eg.random_action(e, A);
     } else {
       int best = 0;
       float bq = q[e * A];
@@ -148,7 +136,7 @@ __global__ __launch_bounds__(256) void epsilon_greedy_kernel(
     }
     actions[e] = a;
   }
-  if (eps_out && blockIdx.x == 0 && threadIdx.x == 0) eps_out[0] = static_cast<float>(eps);
+  if (eps_out && blockIdx.x == 0 && threadIdx.x == 0) eps_out[0] = static_cast<float>(eg.eps);
 }
 
 // The acting step's Q head and epsilon-greedy choice in one launch (dqn_atari_oc.py:345-352:
@@ -178,18 +166,13 @@ __global__ __launch_bounds__(256) void q_head_eps_kernel(
   float4 x[CH];
   head_load_row<CH>(hidden, e, lane, x);
   const float t = head_dots<CH>(x, w, lane) + bias;
-  const int64_t ts = step[0] + step_offset;
-  const double slope = (end_e - start_e) / duration;
-  double eps = slope * static_cast<double>(ts) + start_e;
-  eps = eps > end_e ? eps : end_e;
-  const uint64_t hh = mix64(mix64(seed ^ 0xA0761D6478BD642Full) + static_cast<uint64_t>(ts));
-  const double coin = static_cast<double>(hh >> 11) * (1.0 / 9007199254740992.0);  // [0, 1)
+  const EpsGreedy eg(seed, step[0] + step_offset, start_e, end_e, duration);
   float q[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) q[j] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 8 * j));
   int64_t a;
-  if (coin < eps) {
-    a = static_cast<int64_t>(mix64(hh + static_cast<uint64_t>(e) + 1) % static_cast<uint64_t>(A));
+  if (eg.explore) {
+    a = eg.random_action(e, A);
   } else {
     int best = 0;
     float bqv = q[0];
@@ -204,7 +187,7 @@ __global__ __launch_bounds__(256) void q_head_eps_kernel(
   if (lane == 0) actions[e] = a;
   const float mine = __shfl(t, 8 * (lane & 7), kWave);  // all lanes take part in the permute
   if (q_out && lane < A) q_out[e * A + lane] = mine;
-  if (eps_out && e == 0 && lane == 0) eps_out[0] = static_cast<float>(eps);
+  if (eps_out && e == 0 && lane == 0) eps_out[0] = static_cast<float>(eg.eps);
 }
 
 // Fused TD target + MSE loss, forward and backward w.r.t. q (dqn_atari_oc.py:378-382):
@@ -304,12 +287,8 @@ __global__ __launch_bounds__(256) void dqn_act_step_kernel(DqnActArgs p) {
       for (int c = 0; c < CH; ++c)
         w[j][c] = j < p.A ? reinterpret_cast<const float4*>(p.wq + static_cast<int64_t>(j) * H)[c * kWave + lane]
                           : make_float4(0.f, 0.f, 0.f, 0.f);
-    const int64_t ts = p.step[0] + p.step_offset;
-    const double slope = (p.end_e - p.start_e) / p.duration;
-    double eps = slope * static_cast<double>(ts) + p.start_e;
-    eps = eps > p.end_e ? eps : p.end_e;
-    const uint64_t hh = mix64(mix64(p.seed ^ 0xA0761D6478BD642Full) + static_cast<uint64_t>(ts));
-    const double coin = static_cast<double>(hh >> 11) * (1.0 / 9007199254740992.0);  // [0, 1)
+    // the step's part once per thread, before the wave's loop over its envs
+    const EpsGreedy eg(p.seed, p.step[0] + p.step_offset, p.start_e, p.end_e, p.duration);
     for (int64_t e = wv; e < E; e += 4) {  // wave-uniform
       float4 x[CH];
       head_load_row<CH>(p.hidden, e, lane, x);
@@ -318,8 +297,8 @@ __global__ __launch_bounds__(256) void dqn_act_step_kernel(DqnActArgs p) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) q[j] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 8 * j));
       int64_t a;
-      if (coin < eps) {
-        a = static_cast<int64_t>(mix64(hh + static_cast<uint64_t>(e) + 1) % static_cast<uint64_t>(p.A));
+      if (eg.explore) {
+        a = eg.random_action(e, p.A);
       } else {
         int best = 0;
         float bqv = q[0];
@@ -336,7 +315,7 @@ __global__ __launch_bounds__(256) void dqn_act_step_kernel(DqnActArgs p) {
         s_act[e] = a;
       }
     }
-    if (p.eps_out && threadIdx.x == 0) p.eps_out[0] = static_cast<float>(eps);
+    if (p.eps_out && threadIdx.x == 0) p.eps_out[0] = static_cast<float>(eg.eps);
   }
   __syncthreads();
   // 2. the env step on those actions (object frames)

@@ -22,19 +22,13 @@
 #include <math.h>
 
 #include "ocppo_common.h"
+#include "ocppo_rng.h"
 
 namespace ocppo {
 
 constexpr int kPerMaxNStep = 8;
 constexpr int kPerMaxBatch = 1024;
 enum { kPerPos = 0, kPerSize = 1, kPerMaxPrio = 2, kPerFill = 3, kPerHead = 4 };
-
-__device__ __forceinline__ uint64_t per_mix64(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
 
 struct PerPows {
   double g[kPerMaxNStep];  // gamma ** i, formed by the host
@@ -249,10 +243,10 @@ __global__ __launch_bounds__(kPerMaxBatch) void per_sample_kernel(
     if (ub_in) {
       ub = ub_in[i];
     } else {
-      const uint64_t h = per_mix64(per_mix64(seed ^ 0x2545F4914F6CDD1Dull) +
+      const uint64_t h = splitmix64(splitmix64(seed ^ 0x2545F4914F6CDD1Dull) +
                                    static_cast<uint64_t>(ctr) * 0x100000001B3ull +
                                    static_cast<uint64_t>(i));
-      const double u = static_cast<double>(h >> 11) * (1.0 / 9007199254740992.0);  // [0, 1)
+      const double u = unit53(h);
       ub = static_cast<double>(a) + (static_cast<double>(b) - static_cast<double>(a)) * u;
     }
     if (ub_out) ub_out[i] = ub;

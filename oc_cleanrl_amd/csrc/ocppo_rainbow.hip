@@ -53,23 +53,10 @@ __device__ __forceinline__ int duel_greedy(const float* __restrict__ value,
   const float v0 = h0 ? value[r * N + lane] : 0.f, v1 = h1 ? value[r * N + lane + kWave] : 0.f;
   float m0, m1;
   duel_mean(adv, A, N, lane, h0, h1, m0, m1);
-  int best = 0;
-  float bq = 0.f;
-  for (int j0 = 0; j0 < A; j0 += kC51Batch) {
-    float p0[kC51Batch], p1[kC51Batch], q[kC51Batch];
-    const int valid = A - j0 < kC51Batch ? A - j0 : kC51Batch;
+  return greedy_scan(A, lane, q_out ? q_out + r * A : nullptr,
+                     [&](int j0, int valid, auto& p0, auto& p1, auto& q) {
     duel_softmax_q<kC51Batch>(adv, v0, v1, m0, m1, j0, valid, N, lane, h0, h1, z0, z1, p0, p1, q);
-#pragma unroll
-    for (int g = 0; g < kC51Batch; ++g)
-      if (g < valid) {
-        if (j0 + g == 0 || c51_better(q[g], bq)) {
-          bq = q[g];
-          best = j0 + g;
-        }
-        if (q_out && lane == 0) q_out[r * A + j0 + g] = q[g];
-      }
-  }
-  return best;
+  }).best;
 }
 
 // Fused Rainbow train-step loss (rainbow_atari_oc.py:655-701), forward and d loss / d (value,
@@ -77,20 +64,14 @@ __device__ __forceinline__ int duel_greedy(const float* __restrict__ value,
 //   double Q (:657-669): best = argmax_a sum_k softmax(duel(value_no, adv_no)[b, a])_k z_k of the
 //     ONLINE net on next_obs (first maximum); p' = softmax(duel(value_nt, adv_nt)[b, best]) of
 //     the TARGET net on next_obs
-//   projection (:672-692, not C51's text): next_atoms = r + (f32(gamma_n) * z) * (1 - d);
-//     tz = clamp(next_atoms, v_min, v_max); b = (tz - v_min) / f32(delta_z) with the HOST's
-//     delta_z = (v_max - v_min) / (N - 1); l = floor(b), u = ceil(b), both clamped to
-//     [0, N - 1]; d_m_l = (u + (l == b) - b) * p', d_m_u = (b - l) * p'; target[l] += d_m_l then
-//     target[u] += d_m_u, each in ascending source-atom order (index_add_ on the CPU): every
-//     lane GATHERS its own target atoms from the wave's LDS copy, no float atomic
-//   online side (:695-701): p = softmax(duel(value, adv)[b, a_b]); c = clamp(p, 1e-5, 1 - 1e-5);
-//     loss_b = -sum_k target_k * log(c_k) (an output: the new priorities);
-//     loss = mean_b loss_b * w_b; g_k = in range ? (-((1 / B) * w_b) * target_k) / c_k : 0;
-//     dq_k = (g_k - sum_j g_j p_j) * p_k; dvalue[b, k] = dq_k;
-//     dadvantage[b, a, k] = (a == a_b ? dq_k : 0) + (-dq_k / A): every element is written
-//   stats = {loss, mean_b sum_k p_k z_k} (:708-713): per wave in ascending sample order, then
-//     the waves in order by thread 0, which rewrites both (graph-replay safe); the second one's
-//     sums run in f64
+//   projection (:672-692, not C51's text): gamma ** n_step, the HOST's delta_z =
+//     (v_max - v_min) / (N - 1) rounded to f32, and the (l == b) rule (ocppo_distributional.h:
+//     proj_terms / proj_gather)
+//   online side (:695-701): p = softmax(duel(value, adv)[b, a_b]); loss_b, the clamped cross
+//     entropy (an output: the new priorities), and its backward with scale -((1 / B) * w_b)
+//     (ce_softmax_bwd); loss = mean_b loss_b * w_b; dvalue[b, k] = d_k;
+//     dadvantage[b, a, k] = (a == a_b ? d_k : 0) + (-d_k / A): every element is written
+//   stats = {loss, mean_b sum_k p_k z_k} (:708-713, loss_stats); the second one's sums run in f64
 __global__ __launch_bounds__(kC51LossWaves* kWave) void rainbow_loss_kernel(
     const float* __restrict__ value, const float* __restrict__ adv,
     const float* __restrict__ value_no, const float* __restrict__ adv_no,
@@ -101,17 +82,12 @@ __global__ __launch_bounds__(kC51LossWaves* kWave) void rainbow_loss_kernel(
     float v_max, float delta_z, float inv_b, float* __restrict__ dvalue, float* __restrict__ dadv,
     float* __restrict__ loss_per_sample, float* __restrict__ stats,
     float* __restrict__ target_out, int64_t* __restrict__ best_out) {
-  __shared__ int s_l[kC51LossWaves][kC51MaxAtoms];
-  __shared__ int s_u[kC51LossWaves][kC51MaxAtoms];
-  __shared__ float s_dml[kC51LossWaves][kC51MaxAtoms];
-  __shared__ float s_dmu[kC51LossWaves][kC51MaxAtoms];
-  __shared__ float s_part[kC51LossWaves];
-  __shared__ double s_partq[kC51LossWaves];
+  __shared__ ProjScratch s_proj;
+  __shared__ float s_loss[kC51LossWaves];
+  __shared__ double s_q[kC51LossWaves];
   const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
   const bool h0 = lane < N, h1 = lane + kWave < N;
   const float z0 = h0 ? support[lane] : 0.f, z1 = h1 ? support[lane + kWave] : 0.f;
-  const float n1 = static_cast<float>(N - 1);
-  const float lo = 1e-5f, hi = static_cast<float>(1.0 - 1e-5);
   const float fa = static_cast<float>(A);
   float acc_loss = 0.f;
   double acc_q = 0.0;
@@ -128,48 +104,15 @@ __global__ __launch_bounds__(kC51LossWaves* kWave) void rainbow_loss_kernel(
       float m0, m1, tp0[1], tp1[1], tq[1];
       duel_mean(at, A, N, lane, h0, h1, m0, m1);
       duel_softmax_q<1>(at, v0, v1, m0, m1, best, 1, N, lane, h0, h1, z0, z1, tp0, tp1, tq);
-      // the projection's per-source-atom terms
-      const float r = rewards[b], nd = 1.0f - dones[b];
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int k = lane + h * kWave;
-        if (k < N) {
-          const float z = h ? z1 : z0, p = h ? tp1[0] : tp0[0];
-          const float na = r + (gamma_n * z) * nd;
-          const float tz = fminf(fmaxf(na, v_min), v_max);
-          const float bj = (tz - v_min) / delta_z;
-          const float l = fminf(fmaxf(floorf(bj), 0.f), n1);
-          const float u = fminf(fmaxf(ceilf(bj), 0.f), n1);
-          s_l[wv][k] = static_cast<int>(l);
-          s_u[wv][k] = static_cast<int>(u);
-          s_dml[wv][k] = (u + (l == bj ? 1.0f : 0.0f) - bj) * p;
-          s_dmu[wv][k] = (bj - l) * p;
-        }
-      }
+      proj_terms<false>(s_proj, wv, lane, N, z0, z1, tp0[0], tp1[0], rewards[b], 1.0f - dones[b],
+                        gamma_n, v_min, v_max, delta_z);
     }
     __syncthreads();
     if (active) {
-      float t0 = 0.f, t1 = 0.f;
-      for (int j = 0; j < N; ++j) {
-        const int l = s_l[wv][j];
-        const float v = s_dml[wv][j];
-        if (l == lane) t0 += v;
-        if (l == lane + kWave) t1 += v;
-      }
-      for (int j = 0; j < N; ++j) {
-        const int u = s_u[wv][j];
-        const float v = s_dmu[wv][j];
-        if (u == lane) t0 += v;
-        if (u == lane + kWave) t1 += v;
-      }
-      if (target_out) {
-        if (h0) target_out[b * N + lane] = t0;
-        if (h1) target_out[b * N + lane + kWave] = t1;
-      }
-      // online side: the taken action's pmf (an action outside [0, A) reads the nearest row
-      // instead of past the buffer)
-      int64_t a = actions[b];
-      a = a < 0 ? 0 : (a >= A ? A - 1 : a);
+      float t0, t1;
+      proj_gather(s_proj, wv, lane, N, target_out ? target_out + b * N : nullptr, t0, t1);
+      // online side: the taken action's pmf
+      const int64_t a = clamp_action(actions[b], A);
       const float* ao = adv + b * A * N;
       const float v0 = h0 ? value[b * N + lane] : 0.f;
       const float v1 = h1 ? value[b * N + lane + kWave] : 0.f;
@@ -177,46 +120,25 @@ __global__ __launch_bounds__(kC51LossWaves* kWave) void rainbow_loss_kernel(
       duel_mean(ao, A, N, lane, h0, h1, m0, m1);
       duel_softmax_q<1>(ao, v0, v1, m0, m1, static_cast<int>(a), 1, N, lane, h0, h1, z0, z1, p0,
                         p1, q);
-      const float c0 = fminf(fmaxf(p0[0], lo), hi), c1 = fminf(fmaxf(p1[0], lo), hi);
-      const float e0 = h0 ? t0 * logf(c0) : 0.f, e1 = h1 ? t1 * logf(c1) : 0.f;
-      const float loss_b = -wave_sum(e0 + e1);
       const float w = weights[b];
-      if (lane == 0) loss_per_sample[b] = loss_b;
-      acc_loss += loss_b * w;
+      const CeBwd ce = ce_softmax_bwd(t0, t1, p0[0], p1[0], h0, h1, -(inv_b * w));
+      if (lane == 0) loss_per_sample[b] = ce.loss_b;
+      acc_loss += ce.loss_b * w;
       // the logged q_values is a small difference of large terms (the support is symmetric):
       // its sums run in f64 over the f32 pmf, so only the pmf's own rounding is left in it
       acc_q += wave_sum(static_cast<double>(p0[0]) * z0 + static_cast<double>(p1[0]) * z1);
-      const float gb = -(inv_b * w);
-      const float g0 = (h0 && p0[0] >= lo && p0[0] <= hi) ? (gb * t0) / c0 : 0.f;
-      const float g1 = (h1 && p1[0] >= lo && p1[0] <= hi) ? (gb * t1) / c1 : 0.f;
-      const float sg = wave_sum(g0 * p0[0] + g1 * p1[0]);
-      const float d0 = (g0 - sg) * p0[0], d1 = (g1 - sg) * p1[0];
-      const float sh0 = -(d0 / fa), sh1 = -(d1 / fa);  // the mean's share, every action row
-      if (h0) dvalue[b * N + lane] = d0;
-      if (h1) dvalue[b * N + lane + kWave] = d1;
+      const float sh0 = -(ce.d0 / fa), sh1 = -(ce.d1 / fa);  // the mean's share, every action row
+      if (h0) dvalue[b * N + lane] = ce.d0;
+      if (h1) dvalue[b * N + lane + kWave] = ce.d1;
       for (int j = 0; j < A; ++j) {
         float* out = dadv + (b * A + j) * N;
-        if (h0) out[lane] = j == a ? d0 + sh0 : sh0;
-        if (h1) out[lane + kWave] = j == a ? d1 + sh1 : sh1;
+        if (h0) out[lane] = j == a ? ce.d0 + sh0 : sh0;
+        if (h1) out[lane + kWave] = j == a ? ce.d1 + sh1 : sh1;
       }
     }
     __syncthreads();  // the wave's LDS rows are rewritten by its next sample
   }
-  if (lane == 0) {
-    s_part[wv] = acc_loss;
-    s_partq[wv] = acc_q;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float sl = s_part[0];
-    double sq = s_partq[0];
-    for (int w = 1; w < kC51LossWaves; ++w) {
-      sl += s_part[w];
-      sq += s_partq[w];
-    }
-    stats[0] = sl / static_cast<float>(B);                            // losses/td_loss
-    stats[1] = static_cast<float>(sq / static_cast<double>(B));  // losses/q_values
-  }
+  loss_stats(acc_loss, acc_q, s_loss, s_q, lane, wv, B, stats);
 }
 
 // The acting step (:617-620): q_dist = q_network(obs); argmax_a sum_k q_dist * support. One wave

@@ -4,15 +4,10 @@
 // (ocppo_loss.hip): one definition, bitwise the same frames either way.
 #pragma once
 #include "ocppo_common.h"
+#include "ocppo_rng.h"
 
 namespace ocppo {
 
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
 __device__ __forceinline__ float unit24(uint64_t h) {  // exact multiple of 2^-24 in [0, 1)
   return static_cast<float>(h >> 40) * (1.0f / 16777216.0f);
 }

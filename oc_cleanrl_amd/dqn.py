@@ -38,7 +38,7 @@ import torch
 import torch.nn as nn
 
 from . import gemm_table, ops
-from .agents import Predictor, fused_trunk, q_head
+from .agents import Predictor, fused_trunk, nature_cnn, object_trunk, q_head
 from .args import OBS_MODES, parse_dataclass
 from .envs import SyntheticAtariEnv
 
@@ -101,12 +101,8 @@ class QNetwork(Predictor):
 
     def __init__(self, obs_shape, n_actions):
         super().__init__()
-        self.network = nn.Sequential(
-            nn.Conv2d(obs_shape[0], 32, 8, stride=4), nn.ReLU(),
-            nn.Conv2d(32, 64, 4, stride=2), nn.ReLU(),
-            nn.Conv2d(64, 64, 3, stride=1), nn.ReLU(),
-            nn.Flatten(), nn.Linear(3136, 512), nn.ReLU(),
-            nn.Linear(512, n_actions))
+        self.network = nn.Sequential(*nature_cnn(obs_shape[0]), nn.Linear(3136, 512), nn.ReLU(),
+                                     nn.Linear(512, n_actions))
 
     def forward(self, x):
         return self.network(x / 255.0)
@@ -133,17 +129,8 @@ class QNetworkObj(Predictor):
     def __init__(self, obs_shape, n_actions, encoder_dims=(256, 512, 1024, 512),
                  decoder_dims=(512,)):
         super().__init__()
-        layers, d = [], obs_shape[-1]
-        for l in encoder_dims:
-            layers += [nn.Linear(d, l), nn.ReLU()]
-            d = l
-        layers.append(nn.Flatten())
-        d *= int(np.prod(obs_shape[:-1]))
-        for l in decoder_dims:
-            layers += [nn.Linear(d, l), nn.ReLU()]
-            d = l
-        layers.append(nn.Linear(d, n_actions))
-        self.network = nn.Sequential(*layers)
+        layers, d = object_trunk(obs_shape, encoder_dims, decoder_dims)
+        self.network = nn.Sequential(*layers, nn.Linear(d, n_actions))
 
     def forward(self, x):
         return self.network(x)
@@ -155,10 +142,9 @@ class QNetworkObj(Predictor):
     predict = QNetwork.predict
 
 
-# The train step's target-network forward on a side stream, concurrent with the online forward
-# (DQNTrainer._train_step; captured into the chunk's hipGraph as a fork / join): measured slower
-# (config 5 11.3k vs 12.4k env steps/s, profiles/r06/config5_side_stream/), so off
-TARGET_SIDE_STREAM = False
+# Tried and removed: the train step's target-network forward on a side stream, concurrent with the
+# online forward (captured into the chunk's hipGraph as a fork / join), measured slower (config 5
+# 11.3k vs 12.4k env steps/s, profiles/r06/config5_side_stream/).
 
 # The acting step's Q head + epsilon-greedy choice as one HIP launch (ops.q_head_epsilon_greedy).
 FUSED_ACT = True
@@ -171,11 +157,6 @@ def make_qnet(args: DQNArgs, obs_shape, n_actions) -> nn.Module:
     if args.obs_mode == "obj":
         return QNetworkObj(obs_shape, n_actions, args.encoder_dims, args.decoder_dims)
     return QNetwork(obs_shape, n_actions)
-
-
-def _q_forward(net, x):
-    """Q(x) through the fused Linear(+ReLU) path (same math as net(x))."""
-    return net.q_values(x)
 
 
 class DQNTrainer:
@@ -241,7 +222,6 @@ class DQNTrainer:
                       "rewards": torch.zeros((B, 1), device=dev),
                       "dones": torch.zeros((B, 1), device=dev)}
         self.dq = torch.zeros((B, self.A), dtype=f32, device=dev)
-        self.side = torch.cuda.Stream(self.dev) if self.dev.type == "cuda" else None
         self.td_stats = torch.zeros(2, dtype=f32, device=dev)
         self.duration = a.exploration_fraction * a.total_timesteps
         # acting: the Q head and the epsilon-greedy choice in one launch
@@ -273,7 +253,7 @@ class DQNTrainer:
     def _act(self, k: int):
         """Greedy / random actions of global step chunk base + k + 1 from the whole network."""
         a = self.args
-        q = _q_forward(self.q, self.net_obs)
+        q = self.q.q_values(self.net_obs)
         ops.epsilon_greedy(q, a.seed, self.step_dev, a.start_e, a.end_e, self.duration,
                            self.actions, self.epsilon, step_offset=k + 1)
 
@@ -322,21 +302,9 @@ class DQNTrainer:
         """:377-392 — sample, TD target + MSE (fused), backward, Adam."""
         a = self.args
         d = self.rb.sample(a.batch_size, out=self.batch)
-        if TARGET_SIDE_STREAM and self.side is not None:
-            # the target network's forward on a side stream beside the online forward: two
-            # independent launch chains (5 launches each) of one sampled batch, joined before the
-            # TD loss -- the same kernels on the same operands, so the same values
-            main = torch.cuda.current_stream(self.dev)
-            self.side.wait_stream(main)
-            with torch.cuda.stream(self.side), torch.no_grad():
-                q_next = _q_forward(self.target, d["next_observations"])
-            q = _q_forward(self.q, d["observations"])
-            main.wait_stream(self.side)
-            q_next.record_stream(main)
-        else:
-            with torch.no_grad():
-                q_next = _q_forward(self.target, d["next_observations"])
-            q = _q_forward(self.q, d["observations"])
+        with torch.no_grad():
+            q_next = self.target.q_values(d["next_observations"])
+        q = self.q.q_values(d["observations"])
         ops.td_loss_fwd_bwd(q.detach(), q_next, d["actions"], d["rewards"], d["dones"], a.gamma,
                             dq=self.dq, stats=self.td_stats)
         if not self.direct_grads:
@@ -412,14 +380,20 @@ class DQNTrainer:
                 if gs % a.target_network_frequency == 0:
                     self._target_update()
 
+    # metrics(): the learner's key spellings (its reference script's writer.add_scalar names)
+    LOSS_KEY = "losses/td_loss"
+    EPISODE_KEYS = ("charts/Episodic_Original_Reward", "charts/Episodic_Length")
+
+    def _chart(self) -> dict:
+        return {"charts/epsilon": float(self.epsilon)}
+
     def metrics(self) -> dict:
         st = self.td_stats.tolist()
         ep_ret, ep_len, ep_n = self.env.pop_episode_stats()
-        m = {"losses/td_loss": st[0], "losses/q_values": st[1],
-             "charts/epsilon": float(self.epsilon)}
+        m = {self.LOSS_KEY: st[0], "losses/q_values": st[1], **self._chart()}
         if ep_n > 0:
-            m["charts/Episodic_Original_Reward"] = ep_ret / ep_n
-            m["charts/Episodic_Length"] = ep_len / ep_n
+            m[self.EPISODE_KEYS[0]] = ep_ret / ep_n
+            m[self.EPISODE_KEYS[1]] = ep_len / ep_n
         return m
 
     def checkpoint(self) -> dict:
@@ -428,9 +402,24 @@ class DQNTrainer:
                 "args": asdict(self.args)}
 
 
-def run_dqn(args: DQNArgs, device=None) -> DQNTrainer:
+def check_atoms(n_atoms: int) -> None:
+    """The distributional kernels' atom limit (C51Trainer, RainbowTrainer: before the env is made)."""
+    if not (2 <= n_atoms <= ops.C51_MAX_ATOMS):
+        raise ValueError(f"n_atoms={n_atoms}: need 2 <= n_atoms <= {ops.C51_MAX_ATOMS}")
+
+
+def check_actions(n_actions: int, name: str) -> None:
+    """... and their action limit (once the env has said how many there are)."""
+    if n_actions > ops.C51_MAX_ACTIONS:
+        raise ValueError(f"{n_actions} actions: the {name} kernels take at most "
+                         f"{ops.C51_MAX_ACTIONS}")
+
+
+def run_learner(trainer_cls, args, device=None, always_save: bool = False):
+    """The run loop of the three value-based learners: steps in chunks of about `log_every`, one
+    metrics.jsonl line per chunk, the final model when `save_model` (or always)."""
     device = device or torch.device("cuda:0")
-    tr = DQNTrainer(args, device)
+    tr = trainer_cls(args, device)
     run_name = f"{args.env_id}__{args.exp_name}__{args.seed}__{int(time.time())}".replace("/", "_")
     run_dir = Path(args.log_dir) / run_name
     run_dir.mkdir(parents=True, exist_ok=True)
@@ -448,17 +437,25 @@ def run_dqn(args: DQNArgs, device=None) -> DQNTrainer:
             m["charts/SPS"] = int(tr.global_step * args.num_envs / (time.time() - start))
             m["global_step"] = tr.global_step
             w.write(json.dumps(m) + "\n")
-    if args.save_model:
+    if always_save or args.save_model:
         torch.save(tr.checkpoint(), run_dir / f"{args.exp_name}.cleanrl_model")
     return tr
 
 
-def main(argv=None):
-    args = parse_dataclass(DQNArgs, argv, None, "oc_cleanrl_amd DQN (dqn_atari_oc.py surface)")
+def run_dqn(args: DQNArgs, device=None) -> DQNTrainer:
+    return run_learner(DQNTrainer, args, device)
+
+
+def learner_main(args_cls, run, description: str, argv=None):
+    args = parse_dataclass(args_cls, argv, None, description)
     if args.obs_mode not in OBS_MODES:
         raise SystemExit(f"bad obs_mode {args.obs_mode}")
-    tr = run_dqn(args)
+    tr = run(args)
     print({k: round(v, 5) for k, v in tr.metrics().items()})
+
+
+def main(argv=None):
+    learner_main(DQNArgs, run_dqn, "oc_cleanrl_amd DQN (dqn_atari_oc.py surface)", argv)
 
 
 if __name__ == "__main__":

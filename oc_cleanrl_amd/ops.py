@@ -2506,18 +2506,19 @@ def td_loss_fwd_bwd(q, q_next, actions, rewards, dones, gamma: float, dq=None, s
 C51_MAX_ATOMS, C51_MAX_ACTIONS = 128, 18
 
 
-def _c51_shape(logits, atoms, name: str):
-    """(rows, A, N) of [rows, A * N] logits against the [N] atoms buffer."""
-    if not isinstance(logits, torch.Tensor) or logits.dim() != 2:
-        raise ValueError(f"{name}: expected [rows, A * N] logits")
+def _dist_shape(x, atoms, name: str, atoms_name: str = "atoms"):
+    """(rows, A, N) of a [rows, A * N] head output (C51's logits, Rainbow's advantage) against the
+    [N] support buffer, within the distributional kernels' limits."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise ValueError(f"{name}: expected a [rows, A * N] tensor")
     if not isinstance(atoms, torch.Tensor) or atoms.dim() != 1:
-        raise ValueError("atoms: expected the [N] atoms buffer")
-    rows, AN = logits.shape
+        raise ValueError(f"{atoms_name}: expected the [N] {atoms_name} buffer")
+    rows, AN = x.shape
     N = atoms.shape[0]
     if not 2 <= N <= C51_MAX_ATOMS:
-        raise ValueError(f"atoms: N={N}, need 2 <= N <= {C51_MAX_ATOMS}")
+        raise ValueError(f"{atoms_name}: N={N}, need 2 <= N <= {C51_MAX_ATOMS}")
     if rows < 1 or AN % N or not 1 <= AN // N <= C51_MAX_ACTIONS:
-        raise ValueError(f"{name}: shape {tuple(logits.shape)} is not [rows >= 1, A * {N}] with "
+        raise ValueError(f"{name}: shape {tuple(x.shape)} is not [rows >= 1, A * {N}] with "
                          f"1 <= A <= {C51_MAX_ACTIONS}")
     return rows, AN // N, N
 
@@ -2527,7 +2528,7 @@ def c51_epsilon_greedy(logits, atoms, seed: int, step, start_e: float, end_e: fl
                        q_out=None):
     """epsilon_greedy((softmax(logits.view(E, A, N), 2) * atoms).sum(2), ...) in one launch
     (QNetwork_C51.get_action's expected Q + c51_atari_oc.py:303-308)."""
-    E, A, N = _c51_shape(logits, atoms, "logits")
+    E, A, N = _dist_shape(logits, atoms, "logits")
     dev = logits.device
     f = torch.float32
     if actions_out is None:
@@ -2547,7 +2548,7 @@ def c51_loss_fwd_bwd(logits, logits_next, atoms, actions, rewards, dones, gamma:
     Q of the taken actions}, dlogits [B, A * N] = d loss / d logits). target_pmfs [B, N] f32 and
     next_action [B] i64, when given, receive the projected target distribution and the target
     net's greedy next action."""
-    B, A, N = _c51_shape(logits, atoms, "logits")
+    B, A, N = _dist_shape(logits, atoms, "logits")
     dev = logits.device
     f = torch.float32
     if dlogits is None:
@@ -2701,21 +2702,10 @@ class PrioritizedReplay:
 
 def _rainbow_shape(value, advantage, support, name: str):
     """(rows, A, N) of value [rows, N] / advantage [rows, A * N] against the [N] support."""
-    if not isinstance(support, torch.Tensor) or support.dim() != 1:
-        raise ValueError("support: expected the [N] support buffer")
-    N = support.shape[0]
-    if not 2 <= N <= C51_MAX_ATOMS:
-        raise ValueError(f"support: N={N}, need 2 <= N <= {C51_MAX_ATOMS}")
-    if not isinstance(value, torch.Tensor) or value.dim() != 2 or value.shape[1] != N or \
-            value.shape[0] < 1:
-        raise ValueError(f"{name}: value must be [rows >= 1, {N}]")
-    rows = value.shape[0]
-    if not isinstance(advantage, torch.Tensor) or advantage.dim() != 2 or \
-            advantage.shape[0] != rows or advantage.shape[1] % N or \
-            not 1 <= advantage.shape[1] // N <= C51_MAX_ACTIONS:
-        raise ValueError(f"{name}: advantage must be [{rows}, A * {N}] with 1 <= A <= "
-                         f"{C51_MAX_ACTIONS}")
-    return rows, advantage.shape[1] // N, N
+    rows, A, N = _dist_shape(advantage, support, f"{name}: advantage", "support")
+    if not isinstance(value, torch.Tensor) or tuple(value.shape) != (rows, N):
+        raise ValueError(f"{name}: value must be [{rows}, {N}]")
+    return rows, A, N
 
 
 def rainbow_greedy(value, advantage, support, actions_out=None, q_out=None):

@@ -22,11 +22,8 @@ matrices, as in the reference.
 """
 from __future__ import annotations
 
-import json
 import math
-import time
-from dataclasses import asdict, dataclass
-from pathlib import Path
+from dataclasses import dataclass
 from typing import Optional
 
 import numpy as np
@@ -35,9 +32,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .agents import Predictor, fused_trunk, layer_init
-from .args import OBS_MODES, parse_dataclass
-from .dqn import DQNTrainer
+from .agents import Predictor, fused_trunk, layer_init, nature_cnn, object_trunk
+from .dqn import DQNTrainer, check_actions, check_atoms, learner_main, run_learner
 
 
 @dataclass
@@ -142,11 +138,7 @@ class NoisyDuelingDistributionalNetwork(Predictor):
     def __init__(self, obs_shape, n_actions, n_atoms, v_min, v_max):
         super().__init__()
         self._set_support(n_actions, n_atoms, v_min, v_max)
-        self.network = nn.Sequential(
-            nn.Conv2d(obs_shape[0], 32, 8, stride=4), nn.ReLU(),
-            nn.Conv2d(32, 64, 4, stride=2), nn.ReLU(),
-            nn.Conv2d(64, 64, 3, stride=1), nn.ReLU(),
-            nn.Flatten())
+        self.network = nn.Sequential(*nature_cnn(obs_shape[0]))
         self._set_heads(3136)
 
     def _set_support(self, n_actions, n_atoms, v_min, v_max):
@@ -196,15 +188,7 @@ class NoisyDuelingDistributionalPPObj(NoisyDuelingDistributionalNetwork):
                  decoder_dims=(32,)):
         Predictor.__init__(self)
         self._set_support(n_actions, n_atoms, v_min, v_max)
-        layers, d = [], obs_shape[-1]
-        for l in encoder_dims:
-            layers += [layer_init(nn.Linear(d, l)), nn.ReLU()]
-            d = l
-        layers.append(nn.Flatten())
-        d *= int(np.prod(obs_shape[:-1]))
-        for l in decoder_dims:
-            layers += [layer_init(nn.Linear(d, l)), nn.ReLU()]
-            d = l
+        layers, d = object_trunk(obs_shape, encoder_dims, decoder_dims, layer_init)
         self.network = nn.Sequential(*layers)
         self._set_heads(d)
 
@@ -225,12 +209,9 @@ class RainbowTrainer(DQNTrainer):
     def __init__(self, args: RainbowArgs, device, log: bool = True):
         if args.num_envs != 1:  # :513
             raise ValueError("vectorized envs are not supported at the moment (num_envs == 1)")
-        if not (2 <= args.n_atoms <= ops.C51_MAX_ATOMS):
-            raise ValueError(f"n_atoms={args.n_atoms}: need 2 <= n_atoms <= {ops.C51_MAX_ATOMS}")
+        check_atoms(args.n_atoms)
         super().__init__(args, device, log)
-        if self.A > ops.C51_MAX_ACTIONS:
-            raise ValueError(f"{self.A} actions: the Rainbow kernels take at most "
-                             f"{ops.C51_MAX_ACTIONS}")
+        check_actions(self.A, "Rainbow")
         self.fused_act = False  # DQN's Q-head launch does not apply: acting is self._act
         B, N, f = args.batch_size, args.n_atoms, torch.float32
         self.batch = self.rb.new_batch(B)
@@ -279,49 +260,21 @@ class RainbowTrainer(DQNTrainer):
         torch.autograd.backward([value, advantage], [self.dvalue, self.dadvantage])
         self.opt.step()
 
-    def metrics(self) -> dict:
-        st = self.td_stats.tolist()
-        ep_ret, ep_len, ep_n = self.env.pop_episode_stats()
-        m = {"losses/td_loss": st[0], "losses/q_values": st[1],
-             "charts/beta": float(self.rb.beta_dev)}
-        if ep_n > 0:
-            m["charts/episodic_return"] = ep_ret / ep_n
-            m["charts/episodic_length"] = ep_len / ep_n
-        return m
+    EPISODE_KEYS = ("charts/episodic_return", "charts/episodic_length")
+
+    def _chart(self) -> dict:
+        return {"charts/beta": float(self.rb.beta_dev)}
 
 
 def run_rainbow(args: RainbowArgs, device=None) -> RainbowTrainer:
-    device = device or torch.device("cuda:0")
-    tr = RainbowTrainer(args, device)
-    run_name = f"{args.env_id}__{args.exp_name}__{args.seed}__{int(time.time())}".replace("/", "_")
-    run_dir = Path(args.log_dir) / run_name
-    run_dir.mkdir(parents=True, exist_ok=True)
-    (run_dir / "args.json").write_text(json.dumps(asdict(args), indent=1, default=str))
-    start = time.time()
-    chunk = max(args.train_frequency, args.log_every - args.log_every % args.train_frequency)
-    with open(run_dir / "metrics.jsonl", "w") as w:
-        while tr.global_step < args.total_timesteps:
-            n = min(chunk, args.total_timesteps - tr.global_step)
-            n -= n % args.train_frequency if tr._graphable() else 0
-            if n <= 0:
-                break
-            tr.steps(n)
-            m = tr.metrics()
-            m["charts/SPS"] = int(tr.global_step / (time.time() - start))
-            m["global_step"] = tr.global_step
-            w.write(json.dumps(m) + "\n")
-    # :734-739 (the reference always writes the final model)
-    torch.save(tr.checkpoint(), run_dir / f"{args.exp_name}.cleanrl_model")
-    return tr
+    # :734-739: the reference always writes the final model; num_envs == 1, so the shared
+    # SPS = global_step * num_envs / elapsed is the reference's global_step / elapsed
+    return run_learner(RainbowTrainer, args, device, always_save=True)
 
 
 def main(argv=None):
-    args = parse_dataclass(RainbowArgs, argv, None,
-                           "oc_cleanrl_amd Rainbow (rainbow_atari_oc.py surface)")
-    if args.obs_mode not in OBS_MODES:
-        raise SystemExit(f"bad obs_mode {args.obs_mode}")
-    tr = run_rainbow(args)
-    print({k: round(v, 5) for k, v in tr.metrics().items()})
+    learner_main(RainbowArgs, run_rainbow, "oc_cleanrl_amd Rainbow (rainbow_atari_oc.py surface)",
+                 argv)
 
 
 if __name__ == "__main__":

@@ -2,22 +2,18 @@
 the loss block they were made from, and the error rule both test files apply."""
 from __future__ import annotations
 
-import functools
-
 import numpy as np
 import torch
 
-from conftest import golden
+import dist_util
+from dist_util import F32_FLOOR, rel_err  # noqa: F401  (the test files import them from here)
 
 FIXTURES = ("b32_a6_n51", "ties", "peaked", "b7_a18_n101")
 CHECKED = ("target_pmfs", "dlogits", "loss", "q_values")
-F32_FLOOR = 4 * 2.0 ** -23
 
 
-@functools.lru_cache(maxsize=None)
 def fixture(name: str) -> dict:
-    """Loaded once per session and shared; callers must not modify the arrays."""
-    return golden(f"c51_{name}.npz")
+    return dist_util.fixture(name, "c51_")
 
 
 def c51_loss_torch(logits, logits_next, atoms, actions, rewards, dones, gamma, v_min, v_max):
@@ -55,26 +51,12 @@ def restated(z: dict, dtype) -> dict:
     float64 gamma is the value the f32 run rounds it to, as in the fixture's twin."""
     t = lambda k: torch.from_numpy(z[k]).to(dtype)  # noqa: E731
     gamma = float(z["gamma"]) if dtype == torch.float32 else float(np.float32(z["gamma"]))
-    lg = t("logits").requires_grad_(True)
-    out = c51_loss_torch(lg, t("logits_next"), t("atoms"), torch.from_numpy(z["actions"]),
-                         t("rewards"), t("dones"), gamma, float(z["v_min"]), float(z["v_max"]))
-    out["loss"].backward()
-    res = {k: v.detach().numpy() for k, v in out.items()}
-    res["dlogits"] = lg.grad.numpy()
-    return res
-
-
-def rel_err(x, ref64) -> float:
-    """max |x - ref64| relative to ref64's largest element."""
-    ref64 = np.asarray(ref64, np.float64)
-    return float(np.abs(np.asarray(x, np.float64) - ref64).max() / np.abs(ref64).max())
+    args = [t("logits"), t("logits_next"), t("atoms"), torch.from_numpy(z["actions"]),
+            t("rewards"), t("dones"), gamma, float(z["v_min"]), float(z["v_max"])]
+    return dist_util.restated(c51_loss_torch, args, {"dlogits": 0})
 
 
 def bounds(z: dict) -> dict:
     """Per checked tensor: max(3 x the f32 reference's own error against the f64 twin, 4 * 2^-23)
     and that reference error."""
-    out = {}
-    for k in CHECKED:
-        ref = rel_err(z[k], z[k + "64"])
-        out[k] = (max(3 * ref, F32_FLOOR), ref)
-    return out
+    return dist_util.bounds(z, CHECKED)

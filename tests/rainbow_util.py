@@ -4,42 +4,22 @@ torch restatement of the prioritized n-step replay and of the loss block they we
 the oracle at other shapes), and the error rule."""
 from __future__ import annotations
 
-import functools
-
 import numpy as np
 import torch
 
-from conftest import golden
+import dist_util
+from dist_util import F32_FLOOR, bound, fixture, rel_err  # noqa: F401  (imported from here too)
 
 LOSS_FIXTURES = ("b32_a6_n51", "b7_a18_n101", "ties", "edges")
 ADDSEQ_FIXTURES = ("c6_n3", "c8_n1", "c8_n3", "c6_n1")
 SAMPLE_FIXTURES = ("c6", "c8")
 CHECKED = ("target_pmfs", "loss_per_sample", "loss", "q_values", "dvalue", "dadvantage")
-F32_FLOOR = 4 * 2.0 ** -23
 f32 = np.float32
 
 
-@functools.lru_cache(maxsize=None)
-def fixture(name: str) -> dict:
-    """Loaded once per session and shared; callers must not modify the arrays."""
-    return golden(f"{name}.npz")
-
-
-# ---- the error rule -----------------------------------------------------------------------------
-def rel_err(x, ref64) -> float:
-    """max |x - ref64| relative to ref64's largest element."""
-    ref64 = np.asarray(ref64, np.float64)
-    return float(np.abs(np.asarray(x, np.float64) - ref64).max() / np.abs(ref64).max())
-
-
-def bound(ref32, ref64) -> tuple[float, float]:
-    """max(3 x the f32 reference's own error against the f64 twin, 4 * 2^-23), and that error."""
-    ref = rel_err(ref32, ref64)
-    return max(3 * ref, F32_FLOOR), ref
-
-
+# ---- the error rule (dist_util's rel_err / bound) ------------------------------------------------
 def bounds(z: dict) -> dict:
-    return {k: bound(z[k], z[k + "64"]) for k in CHECKED}
+    return dist_util.bounds(z, CHECKED)
 
 
 def check_elementwise(x, ref32, ref64, what=""):
@@ -194,10 +174,5 @@ def loss_args(z: dict, dtype):
 def restated(z: dict, dtype) -> dict:
     """rainbow_loss_torch + autograd on fixture `z` in `dtype`, as numpy arrays."""
     tensors, scalars = loss_args(z, dtype)
-    tensors[0].requires_grad_(True)
-    tensors[1].requires_grad_(True)
-    out = rainbow_loss_torch(*tensors, *scalars)
-    out["loss"].backward()
-    res = {k: v.detach().numpy() for k, v in out.items()}
-    res["dvalue"], res["dadvantage"] = tensors[0].grad.numpy(), tensors[1].grad.numpy()
-    return res
+    return dist_util.restated(rainbow_loss_torch, [*tensors, *scalars],
+                              {"dvalue": 0, "dadvantage": 1})

@@ -136,3 +136,65 @@ def test_fused_act_step_is_the_four_launches(dev, monkeypatch, envs, vecnorm):
         assert torch.equal(x, y)
     for p, q in zip(a.q.parameters(), b.q.parameters()):
         assert torch.equal(p, q)
+
+
+def test_four_epsilon_greedy_routes_agree(dev):
+    """The one epsilon-greedy decision behind four kernels: on the same Q values, seed and global
+    step, ops.epsilon_greedy, ops.q_head_epsilon_greedy (a head that copies q out of the hidden
+    row), ops.c51_epsilon_greedy (one-hot pmfs whose expected values keep q's order) and
+    ops.dqn_act_step (the same head, on a small synthetic env) return equal actions and equal
+    epsilon, on both sides of the coin."""
+    from oc_cleanrl_amd import ops
+    from oc_cleanrl_amd.envs import SyntheticAtariEnv
+
+    E, A, H, N, W, F = 5, 6, 256, 51, 2, 4
+    seed, offset, duration = 11, 3, 100.0
+    rng = np.random.default_rng(5)
+    q_c = torch.from_numpy(rng.standard_normal((E, A)).astype(np.float32))
+    q = q_c.to(dev)
+    # hidden[e, :A] = q[e] and wq[j] = unit vector j: every dot product is q[e, j] plus exact zeros
+    hidden = torch.zeros((E, H), device=dev)
+    hidden[:, :A] = q
+    wq = torch.zeros((A, H), device=dev)
+    wq[torch.arange(A), torch.arange(A)] = 1.0
+    bq = torch.zeros(A, device=dev)
+    # action j of env e puts its mass on atom 5 * (rank of q[e, j]): expected values in q's order
+    rank = q_c.argsort(1).argsort(1)
+    lg = torch.zeros((E, A, N))
+    lg.scatter_(2, (5 * rank).unsqueeze(2), 30.0)
+    logits, atoms = lg.reshape(E, A * N).to(dev), torch.linspace(-10, 10, N).to(dev)
+    # dqn_act_step's surroundings: an object-frame env, the frame stacks and a replay
+    env = SyntheticAtariEnv("ALE/Pong-v5", "obj", E, F, seed, dev, W)
+    f32 = torch.float32
+    stacks = [torch.zeros((E, W, F), dtype=f32, device=dev) for _ in range(2)]
+    net_obs = torch.zeros((E, W, F), dtype=f32, device=dev)
+    ops.obs_reset(env.reset(), stacks[0], net_obs)
+    rb = ops.ReplayBuffer(16, E, (W, F), dev, obs_dtype=f32, seed=seed)
+    done_out, rew_out = torch.zeros(E, device=dev), torch.zeros(E, device=dev)
+    assert ops.dqn_act_step_ok(hidden, wq, env, stacks[0], rb)
+
+    step = torch.zeros(1, dtype=torch.int64, device=dev)
+    eps = [torch.full((1,), -1.0, device=dev) for _ in range(4)]
+    q_head = torch.full((E, A), float("nan"), device=dev)
+    q_c51 = torch.full((E, A), float("nan"), device=dev)
+    greedy_seen = set()
+    for t in range(12):
+        step.fill_(t)
+        sched = (seed, step, 0.5, 0.5, duration)
+        acts = [ops.epsilon_greedy(q, *sched, epsilon_out=eps[0], step_offset=offset),
+                ops.q_head_epsilon_greedy(hidden, wq, bq, *sched, epsilon_out=eps[1],
+                                          step_offset=offset, q_out=q_head),
+                ops.c51_epsilon_greedy(logits, atoms, *sched, epsilon_out=eps[2],
+                                       step_offset=offset, q_out=q_c51),
+                ops.dqn_act_step(hidden, wq, bq, *sched, torch.zeros(E, dtype=torch.int64,
+                                                                     device=dev),
+                                 eps[3], offset, env, t, stacks[t % 2], stacks[1 - t % 2],
+                                 net_obs, done_out, rew_out, rb)]
+        assert torch.equal(q_head, q)
+        assert torch.equal(q_c51.argsort(1), q.argsort(1))
+        for a in acts[1:]:
+            assert torch.equal(a, acts[0]), t
+        assert [float(e) for e in eps] == [0.5] * 4
+        assert int(step) == t  # advance = 0: dqn_act_step leaves the counter alone
+        greedy_seen.add(torch.equal(acts[0], torch.argmax(q, 1)))
+    assert greedy_seen == {True, False}
