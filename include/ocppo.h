@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCPPO_ABI_VERSION 31
+#define OCPPO_ABI_VERSION 32
 
 /* status codes */
 #define OCPPO_OK 0
@@ -1157,6 +1157,60 @@ OCPPO_API int ocppo_head_env_store_linear2(
 OCPPO_API int ocppo_cartpole_step(ocppo_stream_t stream, uint64_t seed, const int64_t* actions,
                                   int64_t N, double* state, int64_t* counters, float* obs_out,
                                   float* reward_out, float* done_out, float* ep_state);
+
+/* ---------------------------------------------------------------------------------------------
+ * Object-set transformer blocks (cleanrl/ppo_atari_oc_transformer.py:215-277: PPOAgent's
+ * torch.nn.TransformerEncoderLayer stack, post-norm, batch_first). The two pieces of a block
+ * that are not a Linear; all f32, deterministic (no atomics), graph-capturable.
+ *
+ * ocppo_mha_fwd: masked multi-head self-attention over short sequences, the math path of
+ * nn.MultiheadAttention (torch/nn/functional.py multi_head_attention_forward: q, k, v =
+ * in-proj output split in in_proj_weight's row order, heads = column groups of dh = E / heads;
+ * scaled_dot_product_attention: softmax(q k^T / sqrt(dh) + mask) v with -inf at the keys a
+ * key_padding_mask excludes; heads concatenated for out_proj).
+ *   qkv       : [B, S, 3E] (q | k | v)
+ *   key_valid : [B, S] u8, non-zero = key takes part (the complement of src_key_padding_mask),
+ *               or NULL = every key. Excluded keys get weight exactly 0. A sample with no valid
+ *               key is OUTSIDE THE CONTRACT (torch yields NaN rows there; this kernel's output
+ *               for such a sample is unspecified but finite-or-NaN, never a fault).
+ *   out       : [B, S, E]; every query row is computed, excluded ("padded") rows included
+ *   lse       : [B, heads, S] log-sum-exp of each query's scaled scores over the valid keys
+ * Contract: 1 <= S <= 64, dh = E / heads in {8, 16, 32, 64}, E <= 512, B * heads < 2^31; anything
+ * else returns OCPPO_E_INVALID before any launch.
+ *
+ * ocppo_mha_bwd: its backward. Probabilities are recomputed from qkv and lse; the softmax
+ * backward is dS = P (dP - D) with D = sum_d dout * out per query. Writes EVERY element of
+ * dqkv [B, S, 3E]; dK and dV rows of excluded keys are exactly 0.
+ * ------------------------------------------------------------------------------------------- */
+OCPPO_API int ocppo_mha_fwd(ocppo_stream_t stream, const float* qkv, const uint8_t* key_valid,
+                            int64_t B, int64_t S, int64_t E, int64_t heads, float* out,
+                            float* lse);
+OCPPO_API int ocppo_mha_bwd(ocppo_stream_t stream, const float* qkv, const uint8_t* key_valid,
+                            const float* out, const float* lse, const float* dout, int64_t B,
+                            int64_t S, int64_t E, int64_t heads, float* dqkv);
+
+/* ---------------------------------------------------------------------------------------------
+ * ocppo_add_layernorm_fwd: y = LayerNorm(x + res) * gamma + beta over the last dimension (the
+ * `self.norm1(x + self._sa_block(...))` / `self.norm2(x + self._ff_block(x))` of
+ * torch/nn/modules/transformer.py TransformerEncoderLayer.forward, norm_first = False). Biased
+ * variance taken about the mean in a second pass, as torch's layer_norm; rstd = 1 / sqrt(var + eps).
+ *   x, res, y : [R, E];  gamma, beta : [E];  mean, rstd : [R] (written);  1 <= E <= 512
+ *
+ * ocppo_add_layernorm_bwd: its backward. x + res is RECOMPUTED from the two inputs (not saved).
+ *   dx : [R, E], the one gradient that flows to both addends
+ *   dgamma, dbeta : [E]; per-workgroup partials of a grid that depends on (R, E) only are
+ *   written to the workspace (ocppo_add_layernorm_workspace_bytes(R, E)) and summed in
+ *   workgroup order by a second launch of the same call.
+ * ------------------------------------------------------------------------------------------- */
+OCPPO_API int ocppo_add_layernorm_fwd(ocppo_stream_t stream, const float* x, const float* res,
+                                      const float* gamma, const float* beta, int64_t R, int64_t E,
+                                      double eps, float* y, float* mean, float* rstd);
+OCPPO_API size_t ocppo_add_layernorm_workspace_bytes(int64_t R, int64_t E);
+OCPPO_API int ocppo_add_layernorm_bwd(ocppo_stream_t stream, const float* dy, const float* x,
+                                      const float* res, const float* gamma, const float* mean,
+                                      const float* rstd, int64_t R, int64_t E, float* dx,
+                                      float* dgamma, float* dbeta, void* workspace,
+                                      size_t workspace_bytes);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,430 @@
+// The two non-Linear pieces of a post-norm transformer encoder block, for the object-set PPO agent
+// of cleanrl/ppo_atari_oc_transformer.py:215-277 (torch.nn.TransformerEncoderLayer, batch_first):
+// masked multi-head self-attention over short sequences (S <= 64 objects, head dim 8..64) and the
+// residual add + LayerNorm that follows each half of the block; each with its backward.
+//
+// Attention, rows in lanes: one wave owns one (sample, head) problem. The head's K and V rows sit
+// in LDS (row stride dh + 4 floats, so the per-lane row writes of the backward spread over the
+// banks); lane i holds query row i in registers and walks the keys, every lane reading the same
+// K / V row as one LDS broadcast. The score row is never stored: pass 1 takes its maximum, pass 2
+// recomputes each score, exponentiates and accumulates p * V_j. Excluded keys are skipped (a
+// wave-uniform branch on the ballot of key_valid), which is the exact weight 0 that -inf gives.
+// The backward runs the same walk for dQ, then swaps roles: the lanes' Q and dO rows replace K and
+// V in LDS and lane j, holding K_j and V_j, walks the queries for dK_j and dV_j -- a sum in query
+// order inside one lane, so no atomics and no cross-lane order to fix. Both walks form a score
+// with the same dot product (same operand pairs, same order), so the recomputed probabilities of
+// the two phases are the same bits.
+//
+// Why not v_mfma_f32_16x16x4f32: at the agent's shapes (S = 6..32 objects, dh = 16) a 16 x 16
+// tile is mostly padding, the softmax between the two products needs the score tile moved from the
+// MFMA's column-per-lane layout to a row-wise one through LDS, and the whole problem is ~S^2 dh
+// FMAs per lane-row -- launch-bound, not FLOP-bound.
+#include <math.h>
+
+#include "ocppo_common.h"
+
+namespace ocppo {
+
+constexpr int kAttnMaxS = 64;
+constexpr int kLnMaxE = 512;
+constexpr int kLnPerLane = kLnMaxE / kWave;
+constexpr int kLnWaves = 4;
+constexpr int kLnMaxParts = 128;
+
+// sum_d a[d] * row[d]: four interleaved FMA chains, combined (0 + 1) + (2 + 3). Every score and
+// every dP of this file goes through here with the register operand first.
+template <int DH>
+__device__ __forceinline__ float dot_row(const float (&a)[DH], const float* __restrict__ row) {
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+#pragma unroll
+  for (int c = 0; c < DH / 4; ++c) {
+    const float4 r = *reinterpret_cast<const float4*>(row + 4 * c);
+    s0 = fmaf(a[4 * c + 0], r.x, s0);
+    s1 = fmaf(a[4 * c + 1], r.y, s1);
+    s2 = fmaf(a[4 * c + 2], r.z, s2);
+    s3 = fmaf(a[4 * c + 3], r.w, s3);
+  }
+  return (s0 + s1) + (s2 + s3);
+}
+
+template <int DH>
+__device__ __forceinline__ void axpy_row(float (&acc)[DH], float a, const float* __restrict__ row) {
+#pragma unroll
+  for (int c = 0; c < DH / 4; ++c) {
+    const float4 r = *reinterpret_cast<const float4*>(row + 4 * c);
+    acc[4 * c + 0] = fmaf(a, r.x, acc[4 * c + 0]);
+    acc[4 * c + 1] = fmaf(a, r.y, acc[4 * c + 1]);
+    acc[4 * c + 2] = fmaf(a, r.z, acc[4 * c + 2]);
+    acc[4 * c + 3] = fmaf(a, r.w, acc[4 * c + 3]);
+  }
+}
+
+template <int DH>
+__device__ __forceinline__ void load_row(float (&v)[DH], const float* __restrict__ src) {
+#pragma unroll
+  for (int c = 0; c < DH / 4; ++c) {
+    const float4 r = *reinterpret_cast<const float4*>(src + 4 * c);
+    v[4 * c + 0] = r.x; v[4 * c + 1] = r.y; v[4 * c + 2] = r.z; v[4 * c + 3] = r.w;
+  }
+}
+
+template <int DH>
+__device__ __forceinline__ void store_row(float* __restrict__ dst, const float (&v)[DH], float mul) {
+#pragma unroll
+  for (int c = 0; c < DH / 4; ++c)
+    *reinterpret_cast<float4*>(dst + 4 * c) = make_float4(
+        v[4 * c + 0] * mul, v[4 * c + 1] * mul, v[4 * c + 2] * mul, v[4 * c + 3] * mul);
+}
+
+// S rows of DH floats at `src` (row stride `stride` floats) -> an LDS tile of row stride DH + 4
+template <int DH>
+__device__ __forceinline__ void stage_tile(float* tile, const float* __restrict__ src, int S,
+                                           int64_t stride, int lane) {
+  constexpr int V = DH / 4, LD = DH + 4;
+  for (int idx = lane; idx < S * V; idx += kWave) {
+    const int r = idx / V, c = idx % V;
+    *reinterpret_cast<float4*>(tile + r * LD + 4 * c) =
+        *reinterpret_cast<const float4*>(src + r * stride + 4 * c);
+  }
+}
+
+__device__ __forceinline__ uint64_t key_mask(const uint8_t* __restrict__ key_valid, int64_t b,
+                                             int S, int lane) {
+  const bool kv = lane < S && (key_valid == nullptr || key_valid[b * S + lane] != 0);
+  return __ballot(kv);
+}
+
+template <int DH>
+__global__ __launch_bounds__(kWave) void mha_fwd_kernel(
+    const float* __restrict__ qkv, const uint8_t* __restrict__ key_valid, int S, int E, int heads,
+    float scale, float* __restrict__ out, float* __restrict__ lse) {
+  constexpr int LD = DH + 4;
+  extern __shared__ float4 s_dyn4[];
+  float* s_k = reinterpret_cast<float*>(s_dyn4);
+  float* s_v = s_k + S * LD;
+  const int lane = threadIdx.x;
+  const int64_t b = blockIdx.x / heads;
+  const int h = blockIdx.x % heads;
+  const int64_t ld = 3 * static_cast<int64_t>(E);
+  const float* base = qkv + b * S * ld + h * DH;
+  stage_tile<DH>(s_k, base + E, S, ld, lane);
+  stage_tile<DH>(s_v, base + 2 * E, S, ld, lane);
+  const uint64_t vmask = key_mask(key_valid, b, S, lane);
+  __syncthreads();
+  if (lane >= S) return;
+  float q[DH];
+  load_row<DH>(q, base + lane * ld);
+  float m = -INFINITY;
+  for (int j = 0; j < S; ++j) {
+    if (!((vmask >> j) & 1)) continue;  // wave-uniform
+    m = fmaxf(m, dot_row<DH>(q, s_k + j * LD) * scale);
+  }
+  float l = 0.f, acc[DH];
+#pragma unroll
+  for (int d = 0; d < DH; ++d) acc[d] = 0.f;
+  for (int j = 0; j < S; ++j) {
+    if (!((vmask >> j) & 1)) continue;
+    const float p = expf(dot_row<DH>(q, s_k + j * LD) * scale - m);
+    l += p;
+    axpy_row<DH>(acc, p, s_v + j * LD);
+  }
+  float* o = out + (b * S + lane) * E + h * DH;
+#pragma unroll
+  for (int c = 0; c < DH / 4; ++c)
+    *reinterpret_cast<float4*>(o + 4 * c) = make_float4(
+        acc[4 * c + 0] / l, acc[4 * c + 1] / l, acc[4 * c + 2] / l, acc[4 * c + 3] / l);
+  lse[(b * heads + h) * S + lane] = m + logf(l);
+}
+
+template <int DH>
+__global__ __launch_bounds__(kWave) void mha_bwd_kernel(
+    const float* __restrict__ qkv, const uint8_t* __restrict__ key_valid,
+    const float* __restrict__ out, const float* __restrict__ lse, const float* __restrict__ dout,
+    int S, int E, int heads, float scale, float* __restrict__ dqkv) {
+  constexpr int LD = DH + 4;
+  extern __shared__ float4 s_dyn4[];
+  float* s_a = reinterpret_cast<float*>(s_dyn4);  // K rows, then Q rows
+  float* s_b = s_a + S * LD;                      // V rows, then dO rows
+  float* s_lse = s_b + S * LD;                    // [kAttnMaxS]
+  float* s_dd = s_lse + kAttnMaxS;                // [kAttnMaxS] D_i = sum_d dO * O
+  const int lane = threadIdx.x;
+  const int64_t b = blockIdx.x / heads;
+  const int h = blockIdx.x % heads;
+  const int64_t ld = 3 * static_cast<int64_t>(E);
+  const float* base = qkv + b * S * ld + h * DH;
+  float* dbase = dqkv + b * S * ld + h * DH;
+  stage_tile<DH>(s_a, base + E, S, ld, lane);
+  stage_tile<DH>(s_b, base + 2 * E, S, ld, lane);
+  const uint64_t vmask = key_mask(key_valid, b, S, lane);
+  __syncthreads();
+  const bool row = lane < S;
+  {
+    // phase A: lane = query i -> dQ_i
+    float q[DH], g_o[DH];
+    float lse_i = 0.f, dd = 0.f;
+    if (row) {
+      load_row<DH>(q, base + lane * ld);
+      load_row<DH>(g_o, dout + (b * S + lane) * E + h * DH);
+      dd = dot_row<DH>(g_o, out + (b * S + lane) * E + h * DH);
+      lse_i = lse[(b * heads + h) * S + lane];
+      float dq[DH];
+#pragma unroll
+      for (int d = 0; d < DH; ++d) dq[d] = 0.f;
+      for (int j = 0; j < S; ++j) {
+        if (!((vmask >> j) & 1)) continue;  // wave-uniform
+        const float p = expf(dot_row<DH>(q, s_a + j * LD) * scale - lse_i);
+        const float ds = p * (dot_row<DH>(g_o, s_b + j * LD) - dd);
+        axpy_row<DH>(dq, ds, s_a + j * LD);
+      }
+      store_row<DH>(dbase + lane * ld, dq, scale);
+    }
+    __syncthreads();  // every lane is done with K and V
+    if (row) {
+      store_row<DH>(s_a + lane * LD, q, 1.f);
+      store_row<DH>(s_b + lane * LD, g_o, 1.f);
+      s_lse[lane] = lse_i;
+      s_dd[lane] = dd;
+    }
+    __syncthreads();
+  }
+  if (!row) return;
+  // phase B: lane = key j -> dK_j, dV_j (queries in order 0..S-1)
+  float dk[DH], dv[DH];
+#pragma unroll
+  for (int d = 0; d < DH; ++d) dk[d] = dv[d] = 0.f;
+  if ((vmask >> lane) & 1) {
+    float k[DH], v[DH];
+    load_row<DH>(k, base + E + lane * ld);
+    load_row<DH>(v, base + 2 * E + lane * ld);
+    for (int i = 0; i < S; ++i) {
+      const float p = expf(dot_row<DH>(k, s_a + i * LD) * scale - s_lse[i]);
+      const float ds = p * (dot_row<DH>(v, s_b + i * LD) - s_dd[i]);
+      axpy_row<DH>(dk, ds, s_a + i * LD);
+      axpy_row<DH>(dv, p, s_b + i * LD);
+    }
+  }
+  store_row<DH>(dbase + E + lane * ld, dk, scale);
+  store_row<DH>(dbase + 2 * E + lane * ld, dv, 1.f);
+}
+
+// ---- residual add + LayerNorm -------------------------------------------------------------------
+// One wave per row; lane l holds columns l, l + 64, ... (E <= 512: at most 8 per lane).
+__global__ __launch_bounds__(kLnWaves* kWave) void add_layernorm_fwd_kernel(
+    const float* __restrict__ x, const float* __restrict__ res, const float* __restrict__ gamma,
+    const float* __restrict__ beta, int64_t R, int E, float eps, float* __restrict__ y,
+    float* __restrict__ mean, float* __restrict__ rstd) {
+  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+  const float inv_e = 1.0f / static_cast<float>(E);
+  for (int64_t r = static_cast<int64_t>(blockIdx.x) * kLnWaves + wv; r < R;
+       r += static_cast<int64_t>(gridDim.x) * kLnWaves) {
+    float z[kLnPerLane];
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < kLnPerLane; ++k) {
+      const int e = lane + k * kWave;
+      z[k] = e < E ? x[r * E + e] + res[r * E + e] : 0.f;
+      s += z[k];
+    }
+    const float mu = wave_sum(s) * inv_e;
+    float sq = 0.f;
+#pragma unroll
+    for (int k = 0; k < kLnPerLane; ++k) {
+      const float d = lane + k * kWave < E ? z[k] - mu : 0.f;
+      sq += d * d;
+    }
+    const float rs = 1.0f / sqrtf(wave_sum(sq) * inv_e + eps);
+#pragma unroll
+    for (int k = 0; k < kLnPerLane; ++k) {
+      const int e = lane + k * kWave;
+      if (e < E) y[r * E + e] = (z[k] - mu) * rs * gamma[e] + beta[e];
+    }
+    if (lane == 0) {
+      mean[r] = mu;
+      rstd[r] = rs;
+    }
+  }
+}
+
+// dx per row, and this workgroup's dgamma / dbeta partial: rows blockIdx * 4 + wave, stepping by
+// the grid, summed per wave in row order, then waves 0..3 in order -> part[blockIdx][2][E]
+__global__ __launch_bounds__(kLnWaves* kWave) void add_layernorm_bwd_kernel(
+    const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ res,
+    const float* __restrict__ gamma, const float* __restrict__ mean,
+    const float* __restrict__ rstd, int64_t R, int E, float* __restrict__ dx,
+    float* __restrict__ part) {
+  __shared__ float s_g[kLnWaves][kLnMaxE], s_b[kLnWaves][kLnMaxE];
+  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+  const float inv_e = 1.0f / static_cast<float>(E);
+  float gm[kLnPerLane], dg[kLnPerLane], db[kLnPerLane];
+#pragma unroll
+  for (int k = 0; k < kLnPerLane; ++k) {
+    const int e = lane + k * kWave;
+    gm[k] = e < E ? gamma[e] : 0.f;
+    dg[k] = db[k] = 0.f;
+  }
+  for (int64_t r = static_cast<int64_t>(blockIdx.x) * kLnWaves + wv; r < R;
+       r += static_cast<int64_t>(gridDim.x) * kLnWaves) {
+    const float mu = mean[r], rs = rstd[r];
+    float xh[kLnPerLane], g[kLnPerLane];
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < kLnPerLane; ++k) {
+      const int e = lane + k * kWave;
+      const bool in = e < E;
+      const float d = in ? dy[r * E + e] : 0.f;
+      xh[k] = in ? ((x[r * E + e] + res[r * E + e]) - mu) * rs : 0.f;
+      g[k] = d * gm[k];
+      s1 += g[k];
+      s2 += g[k] * xh[k];
+      dg[k] += d * xh[k];
+      db[k] += d;
+    }
+    const float c1 = wave_sum(s1) * inv_e, c2 = wave_sum(s2) * inv_e;
+#pragma unroll
+    for (int k = 0; k < kLnPerLane; ++k) {
+      const int e = lane + k * kWave;
+      if (e < E) dx[r * E + e] = rs * ((g[k] - c1) - xh[k] * c2);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < kLnPerLane; ++k) {
+    s_g[wv][lane + k * kWave] = dg[k];
+    s_b[wv][lane + k * kWave] = db[k];
+  }
+  __syncthreads();
+  float* pg = part + static_cast<int64_t>(blockIdx.x) * 2 * E;
+  for (int e = threadIdx.x; e < E; e += kLnWaves * kWave) {
+    float a = s_g[0][e], c = s_b[0][e];
+    for (int w = 1; w < kLnWaves; ++w) {
+      a += s_g[w][e];
+      c += s_b[w][e];
+    }
+    pg[e] = a;
+    pg[E + e] = c;
+  }
+}
+
+// dgamma / dbeta = the partials summed in workgroup order
+__global__ __launch_bounds__(256) void add_layernorm_finish_kernel(
+    const float* __restrict__ part, int nb, int E, float* __restrict__ dgamma,
+    float* __restrict__ dbeta) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= 2 * E) return;
+  float a = 0.f;
+  for (int p = 0; p < nb; ++p) a += part[static_cast<int64_t>(p) * 2 * E + t];
+  if (t < E) dgamma[t] = a;
+  else dbeta[t - E] = a;
+}
+
+inline int ln_parts(int64_t R) {
+  const int64_t nb = ceil_div(R, kLnWaves);
+  return static_cast<int>(nb < kLnMaxParts ? (nb > 0 ? nb : 1) : kLnMaxParts);
+}
+
+inline int mha_check(const char* who, int64_t B, int64_t S, int64_t E, int64_t heads) {
+  OCPPO_REQUIRE(B >= 1 && S >= 1 && S <= kAttnMaxS && E >= 1 && E <= 512 && heads >= 1 &&
+                    E % heads == 0,
+                "%s: bad sizes B=%lld S=%lld E=%lld heads=%lld (B >= 1, 1 <= S <= %d, E <= 512, "
+                "heads | E)", who, (long long)B, (long long)S, (long long)E, (long long)heads,
+                kAttnMaxS);
+  const int64_t dh = E / heads;
+  OCPPO_REQUIRE(dh == 8 || dh == 16 || dh == 32 || dh == 64,
+                "%s: head dim %lld not in {8, 16, 32, 64}", who, (long long)dh);
+  OCPPO_REQUIRE(B * heads <= INT32_MAX, "%s: B * heads = %lld exceeds the grid", who,
+                (long long)(B * heads));
+  return OCPPO_OK;
+}
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+}  // namespace ocppo
+
+using namespace ocppo;
+
+#define OCPPO_MHA_DISPATCH(DHV, CALL) \
+  switch (DHV) {                      \
+    case 8: { constexpr int DH = 8; CALL; break; }   \
+    case 16: { constexpr int DH = 16; CALL; break; } \
+    case 32: { constexpr int DH = 32; CALL; break; } \
+    default: { constexpr int DH = 64; CALL; break; } \
+  }
+
+extern "C" int ocppo_mha_fwd(ocppo_stream_t stream, const float* qkv, const uint8_t* key_valid,
+                             int64_t B, int64_t S, int64_t E, int64_t heads, float* out,
+                             float* lse) {
+  if (int rc = mha_check("ocppo_mha_fwd", B, S, E, heads)) return rc;
+  OCPPO_REQUIRE(qkv && out && lse, "ocppo_mha_fwd: null pointer");
+  OCPPO_REQUIRE(aligned16(qkv) && aligned16(out), "ocppo_mha_fwd: qkv / out not 16-B aligned");
+  const int dh = static_cast<int>(E / heads);
+  const float scale = static_cast<float>(1.0 / sqrt(static_cast<double>(dh)));
+  const size_t lds = 2 * static_cast<size_t>(S) * (dh + 4) * sizeof(float);
+  clear_stale_error();
+  OCPPO_MHA_DISPATCH(dh, hipLaunchKernelGGL(mha_fwd_kernel<DH>, dim3(static_cast<unsigned>(B * heads)),
+                                            dim3(kWave), lds, as_stream(stream), qkv, key_valid,
+                                            (int)S, (int)E, (int)heads, scale, out, lse));
+  return check_launch("ocppo_mha_fwd");
+}
+
+extern "C" int ocppo_mha_bwd(ocppo_stream_t stream, const float* qkv, const uint8_t* key_valid,
+                             const float* out, const float* lse, const float* dout, int64_t B,
+                             int64_t S, int64_t E, int64_t heads, float* dqkv) {
+  if (int rc = mha_check("ocppo_mha_bwd", B, S, E, heads)) return rc;
+  OCPPO_REQUIRE(qkv && out && lse && dout && dqkv, "ocppo_mha_bwd: null pointer");
+  OCPPO_REQUIRE(aligned16(qkv) && aligned16(out) && aligned16(dout) && aligned16(dqkv),
+                "ocppo_mha_bwd: qkv / out / dout / dqkv not 16-B aligned");
+  const int dh = static_cast<int>(E / heads);
+  const float scale = static_cast<float>(1.0 / sqrt(static_cast<double>(dh)));
+  const size_t lds = (2 * static_cast<size_t>(S) * (dh + 4) + 2 * kAttnMaxS) * sizeof(float);
+  clear_stale_error();
+  OCPPO_MHA_DISPATCH(dh, hipLaunchKernelGGL(mha_bwd_kernel<DH>, dim3(static_cast<unsigned>(B * heads)),
+                                            dim3(kWave), lds, as_stream(stream), qkv, key_valid,
+                                            out, lse, dout, (int)S, (int)E, (int)heads, scale,
+                                            dqkv));
+  return check_launch("ocppo_mha_bwd");
+}
+
+extern "C" int ocppo_add_layernorm_fwd(ocppo_stream_t stream, const float* x, const float* res,
+                                       const float* gamma, const float* beta, int64_t R,
+                                       int64_t E, double eps, float* y, float* mean,
+                                       float* rstd) {
+  OCPPO_REQUIRE(R >= 0 && R <= INT32_MAX && E >= 1 && E <= kLnMaxE,
+                "ocppo_add_layernorm_fwd: bad sizes R=%lld E=%lld (R >= 0, 1 <= E <= %d)",
+                (long long)R, (long long)E, kLnMaxE);
+  if (R == 0) return OCPPO_OK;
+  OCPPO_REQUIRE(x && res && gamma && beta && y && mean && rstd,
+                "ocppo_add_layernorm_fwd: null pointer");
+  clear_stale_error();
+  hipLaunchKernelGGL(add_layernorm_fwd_kernel, dim3(grid_for(R, kLnWaves)),
+                     dim3(kLnWaves * kWave), 0, as_stream(stream), x, res, gamma, beta, R, (int)E,
+                     static_cast<float>(eps), y, mean, rstd);
+  return check_launch("ocppo_add_layernorm_fwd");
+}
+
+extern "C" size_t ocppo_add_layernorm_workspace_bytes(int64_t R, int64_t E) {
+  if (R < 0 || E < 1 || E > kLnMaxE) return 0;
+  return static_cast<size_t>(ln_parts(R)) * 2 * static_cast<size_t>(E) * sizeof(float);
+}
+
+extern "C" int ocppo_add_layernorm_bwd(ocppo_stream_t stream, const float* dy, const float* x,
+                                       const float* res, const float* gamma, const float* mean,
+                                       const float* rstd, int64_t R, int64_t E, float* dx,
+                                       float* dgamma, float* dbeta, void* workspace,
+                                       size_t workspace_bytes) {
+  OCPPO_REQUIRE(R >= 1 && R <= INT32_MAX && E >= 1 && E <= kLnMaxE,
+                "ocppo_add_layernorm_bwd: bad sizes R=%lld E=%lld (R >= 1, 1 <= E <= %d)",
+                (long long)R, (long long)E, kLnMaxE);
+  OCPPO_REQUIRE(dy && x && res && gamma && mean && rstd && dx && dgamma && dbeta,
+                "ocppo_add_layernorm_bwd: null pointer");
+  if (!workspace || workspace_bytes < ocppo_add_layernorm_workspace_bytes(R, E))
+    return fail(OCPPO_E_WORKSPACE, "ocppo_add_layernorm_bwd: workspace of %zu bytes, need %zu",
+                workspace_bytes, ocppo_add_layernorm_workspace_bytes(R, E));
+  const int nb = ln_parts(R);
+  float* part = static_cast<float*>(workspace);
+  clear_stale_error();
+  hipLaunchKernelGGL(add_layernorm_bwd_kernel, dim3(nb), dim3(kLnWaves * kWave), 0,
+                     as_stream(stream), dy, x, res, gamma, mean, rstd, R, (int)E, dx, part);
+  if (int rc = check_launch("ocppo_add_layernorm_bwd")) return rc;
+  hipLaunchKernelGGL(add_layernorm_finish_kernel, dim3(static_cast<unsigned>(ceil_div(2 * E, 256))),
+                     dim3(256), 0, as_stream(stream), part, nb, (int)E, dgamma, dbeta);
+  return check_launch("ocppo_add_layernorm_bwd (finish)");
+}

@@ -2754,3 +2754,129 @@ def rainbow_loss_fwd_bwd(value, advantage, value_next_online, advantage_next_onl
          _opt(target_pmfs, "target_pmfs", f, dev, B * N),
          _opt(best_actions, "best_actions", torch.int64, dev, B))
     return stats, loss_per_sample, dvalue, dadvantage
+
+
+# ---------------------------------------------------------------------------------------------
+# transformer encoder blocks (ppo_atari_oc_transformer.py:215-277: torch's TransformerEncoderLayer)
+# ---------------------------------------------------------------------------------------------
+MHA_MAX_S, MHA_MAX_E, MHA_HEAD_DIMS = 64, 512, (8, 16, 32, 64)
+
+
+def mha_shape_ok(S: int, E: int, heads: int) -> bool:
+    """The contract of ocppo_mha_fwd / ocppo_mha_bwd."""
+    return (1 <= S <= MHA_MAX_S and 1 <= E <= MHA_MAX_E and heads >= 1 and E % heads == 0 and
+            E // heads in MHA_HEAD_DIMS)
+
+
+def _mha_shape(qkv, key_valid, heads: int, who: str):
+    if qkv.dim() != 3 or qkv.shape[2] % 3:
+        raise ValueError(f"{who}: qkv must be [B, S, 3E], got {tuple(qkv.shape)}")
+    B, S, E3 = qkv.shape
+    E = E3 // 3
+    if B < 1 or not mha_shape_ok(S, E, heads):
+        raise ValueError(f"{who}: unsupported B={B} S={S} E={E} heads={heads} (mha_shape_ok)")
+    kv = _opt(key_valid, "key_valid", torch.uint8, qkv.device, B * S)
+    return B, S, E, kv
+
+
+def mha_fwd(qkv, key_valid, heads: int, out=None, lse=None):
+    """Masked multi-head self-attention (nn.MultiheadAttention's math): qkv [B, S, 3E] f32 (the
+    in-proj output, q | k | v), key_valid [B, S] u8 or None -> (out [B, S, E], lse [B, heads, S])."""
+    B, S, E, kv = _mha_shape(qkv, key_valid, heads, "mha_fwd")
+    dev, f = qkv.device, torch.float32
+    out = torch.empty((B, S, E), dtype=f, device=dev) if out is None else out
+    lse = torch.empty((B, heads, S), dtype=f, device=dev) if lse is None else lse
+    call("ocppo_mha_fwd", _stream(dev), _check(qkv, "qkv", f, dev), kv, B, S, E, heads,
+         _check(out, "out", f, dev, B * S * E), _check(lse, "lse", f, dev, B * heads * S))
+    return out, lse
+
+
+def mha_bwd(qkv, key_valid, out, lse, dout, heads: int, dqkv=None):
+    """d qkv [B, S, 3E] of mha_fwd (every element written; excluded keys' dK / dV exactly 0)."""
+    B, S, E, kv = _mha_shape(qkv, key_valid, heads, "mha_bwd")
+    dev, f = qkv.device, torch.float32
+    dqkv = torch.empty_like(qkv) if dqkv is None else dqkv
+    call("ocppo_mha_bwd", _stream(dev), _check(qkv, "qkv", f, dev), kv,
+         _check(out, "out", f, dev, B * S * E), _check(lse, "lse", f, dev, B * heads * S),
+         _check(dout, "dout", f, dev, B * S * E), B, S, E, heads,
+         _check(dqkv, "dqkv", f, dev, B * S * 3 * E))
+    return dqkv
+
+
+class _MHA(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, key_valid, heads: int):
+        qkv = qkv.detach().contiguous()
+        out, lse = mha_fwd(qkv, key_valid, heads)
+        ctx.save_for_backward(qkv, key_valid, out, lse)
+        ctx.heads = heads
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        qkv, key_valid, out, lse = ctx.saved_tensors
+        return mha_bwd(qkv, key_valid, out, lse, g.contiguous(), ctx.heads), None, None
+
+
+def mha(qkv, key_valid, heads: int):
+    """Differentiable mha_fwd: [B, S, 3E] -> [B, S, E] (the heads concatenated, for out_proj)."""
+    return _MHA.apply(qkv, key_valid, heads)
+
+
+def _ln_shape(x, res, weight, who: str):
+    E = x.shape[-1]
+    if x.shape != res.shape or weight.numel() != E or not 1 <= E <= MHA_MAX_E:
+        raise ValueError(f"{who}: x {tuple(x.shape)}, res {tuple(res.shape)}, weight "
+                         f"{tuple(weight.shape)} (same shapes, last dim <= {MHA_MAX_E})")
+    return x.numel() // E, E
+
+
+def add_layernorm_fwd(x, res, weight, bias, eps: float):
+    """LayerNorm(x + res) * weight + bias over the last dim -> (y, mean [R], rstd [R])."""
+    R, E = _ln_shape(x, res, weight, "add_layernorm_fwd")
+    dev, f = x.device, torch.float32
+    y = torch.empty_like(x)
+    mean = torch.empty(R, dtype=f, device=dev)
+    rstd = torch.empty(R, dtype=f, device=dev)
+    call("ocppo_add_layernorm_fwd", _stream(dev), _check(x, "x", f, dev), _check(res, "res", f, dev),
+         _check(weight, "weight", f, dev, E), _check(bias, "bias", f, dev, E), R, E, float(eps),
+         y.data_ptr(), mean.data_ptr(), rstd.data_ptr())
+    return y, mean, rstd
+
+
+def add_layernorm_bwd(dy, x, res, weight, mean, rstd):
+    """(dx, dweight, dbias) of add_layernorm_fwd; x + res is recomputed from the two inputs, dx
+    is the gradient of both. Two launches: rows + per-workgroup partials, then their ordered sum."""
+    R, E = _ln_shape(x, res, weight, "add_layernorm_bwd")
+    dev, f = x.device, torch.float32
+    dx = torch.empty_like(x)
+    dw = torch.empty(E, dtype=f, device=dev)
+    db = torch.empty(E, dtype=f, device=dev)
+    nb = int(_lib.LIB.ocppo_add_layernorm_workspace_bytes(R, E))
+    ws = torch.empty(nb // 4, dtype=f, device=dev)  # fully written before it is read
+    call("ocppo_add_layernorm_bwd", _stream(dev), _check(dy, "dy", f, dev, R * E),
+         _check(x, "x", f, dev), _check(res, "res", f, dev), _check(weight, "weight", f, dev, E),
+         _check(mean, "mean", f, dev, R), _check(rstd, "rstd", f, dev, R), R, E, dx.data_ptr(),
+         dw.data_ptr(), db.data_ptr(), ws.data_ptr(), nb)
+    return dx, dw, db
+
+
+class _AddLayerNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, res, weight, bias, eps: float):
+        x, res = x.detach().contiguous(), res.detach().contiguous()
+        w = weight.detach()
+        y, mean, rstd = add_layernorm_fwd(x, res, w, bias.detach(), eps)
+        ctx.save_for_backward(x, res, w, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, res, w, mean, rstd = ctx.saved_tensors
+        dx, dw, db = add_layernorm_bwd(g.contiguous(), x, res, w, mean, rstd)
+        return dx, dx, dw, db, None
+
+
+def add_layernorm(x, res, weight, bias, eps: float = 1e-5):
+    """Differentiable LayerNorm(x + res) * weight + bias (the post-norm step of an encoder block)."""
+    return _AddLayerNorm.apply(x, res, weight, bias, eps)

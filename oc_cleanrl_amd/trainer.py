@@ -340,8 +340,7 @@ class PPOTrainer:
         self.reset_stacks = self.host_env and self.env.reset_stacks
         self.A = self.env.n_actions
         self.obs_shape = self.env.single_obs_shape
-        self.agent = make_agent(a.architecture, self.obs_shape, self.A, self.dev, a.encoder_dims,
-                                a.decoder_dims).to(self.dev)
+        self.agent = self._make_agent().to(self.dev)
         # this agent's update-GEMM route (gemm_x6 or hipBLASLt): per-agent state, not a global
         agents.set_update_gemm(self.agent, a.x6_gemm)
         # NatureCNN in channels_last: MIOpen runs its NHWC kernels without transposing every
@@ -364,8 +363,11 @@ class PPOTrainer:
                             isinstance(self.agent, PPObj) and len(a.encoder_dims) > 0)
         # every parameter's grad is written in place by agents._LinearAct (no zero-fill needed)
         # when the agent is a Linear/ReLU stack owned by the fused optimizer
+        # (an agent with parameters outside `network` that autograd accumulates says so:
+        # grads_in_place = False)
         self.direct_grads = a.fused_optimizer and self.fused_head and all(
-            isinstance(m, (nn.Linear, nn.ReLU, nn.Flatten)) for m in self.agent.network)
+            isinstance(m, (nn.Linear, nn.ReLU, nn.Flatten)) for m in self.agent.network) and \
+            getattr(self.agent, "grads_in_place", True)
         if a.fused_optimizer:
             # every parameter becomes a view of one flat buffer; clip + Adam = 2 HIP launches
             self.optimizer = ops.FlatAdam(self.agent.parameters(), lr=a.learning_rate, eps=1e-5,
@@ -528,6 +530,12 @@ class PPOTrainer:
         self.global_step = 0
         self.last_metrics: dict = {}
         self._reset_env()
+
+    def _make_agent(self) -> nn.Module:
+        """The agent this trainer trains (on the CPU; subclasses build another one)."""
+        a = self.args
+        return make_agent(a.architecture, self.obs_shape, self.A, self.dev, a.encoder_dims,
+                          a.decoder_dims)
 
     def _weight_planes(self):
         """ops.WeightPlanes of the PPObj Linear weights whose update forward / dX run on gemm_x6
@@ -1326,11 +1334,13 @@ def _own_tensors(sd: dict) -> dict:
     return {k: v.detach().clone() for k, v in sd.items()}
 
 
-def run(args: Args, device=None, rank: int = 0, world_size: int = 1) -> PPOTrainer:
-    """The script body: iterations, SPS, metrics JSONL, checkpoints (rank 0)."""
+def run(args: Args, device=None, rank: int = 0, world_size: int = 1,
+        trainer_cls=None) -> PPOTrainer:
+    """The script body: iterations, SPS, metrics JSONL, checkpoints (rank 0). trainer_cls: a
+    PPOTrainer subclass to run instead (transformer.TransformerTrainer)."""
     if device is None:
         device = torch.device(f"cuda:{rank % max(torch.cuda.device_count(), 1)}")
-    tr = PPOTrainer(args, device, rank, world_size)
+    tr = (trainer_cls or PPOTrainer)(args, device, rank, world_size)
     run_name = f"{args.env_id}__{args.exp_name}__{args.seed}__{int(time.time())}".replace("/", "_")
     run_dir = Path(args.log_dir) / run_name
     writer = None
