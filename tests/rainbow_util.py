@@ -1,8 +1,10 @@
 """Shared by the Rainbow tests: the fixtures of tests/golden/gen_golden_rainbow.py, a plain numpy /
 torch restatement of the prioritized n-step replay and of the loss block they were made from
-(written fresh; test_rainbow_cpu.py checks it against every fixture, the GPU tests then use it as
-the oracle at other shapes), and the error rule."""
+(written fresh; test_rainbow_cpu.py checks it against every fixture, test_dist_shapes_gpu.py then
+uses it as the oracle at other shapes, on make_case's seeded inputs), and the error rule."""
 from __future__ import annotations
+
+import functools
 
 import numpy as np
 import torch
@@ -128,19 +130,23 @@ def dueling_dist(value, advantage, A, N):
 
 
 def rainbow_loss_torch(value, advantage, value_no, advantage_no, value_nt, advantage_nt, support,
-                       actions, rewards, dones, weights, gamma_n, v_min, v_max, delta_z):
+                       actions, rewards, dones, weights, gamma_n, v_min, v_max, delta_z, b=None):
     """The Rainbow loss on raw head outputs in the dtype of `value`: double-Q action by the online
     net, the target net's pmf there, the n-step categorical projection (host delta_z, (l == b),
     l and u clamped; lower neighbours added first, then upper), the clamped cross entropy per
-    sample and its importance-weighted mean. `value` / `advantage` may require grad."""
+    sample and its importance-weighted mean. `value` / `advantage` may require grad. `b` [B, N],
+    when given, is the projected index to use in place of the one formed here (projected_index:
+    the f32 one, shared by the f32 run and its twin)."""
     B, N = value.shape
     A = advantage.shape[1] // N
     rows = torch.arange(B)
     with torch.no_grad():
         best = torch.argmax((dueling_dist(value_no, advantage_no, A, N) * support).sum(2), 1)
         next_pmfs = dueling_dist(value_nt, advantage_nt, A, N)[rows, best]
-        next_atoms = rewards.view(B, 1) + gamma_n * support * (1 - dones.view(B, 1))
-        b = (next_atoms.clamp(v_min, v_max) - v_min) / delta_z
+        if b is None:
+            next_atoms = rewards.view(B, 1) + gamma_n * support * (1 - dones.view(B, 1))
+            b = (next_atoms.clamp(v_min, v_max) - v_min) / delta_z
+        b = b.to(value.dtype)
         lo = b.floor().clamp(0, N - 1)
         up = b.ceil().clamp(0, N - 1)
         m_lo = (up + (lo == b).to(b.dtype) - b) * next_pmfs
@@ -171,8 +177,87 @@ def loss_args(z: dict, dtype):
     return tensors, (gamma_n, float(z["v_min"]), float(z["v_max"]), delta_z)
 
 
-def restated(z: dict, dtype) -> dict:
-    """rainbow_loss_torch + autograd on fixture `z` in `dtype`, as numpy arrays."""
+def restated(z: dict, dtype, b=None) -> dict:
+    """rainbow_loss_torch + autograd on fixture `z` in `dtype`, as numpy arrays. `b`: the
+    projected index to use (rainbow_loss_torch)."""
     tensors, scalars = loss_args(z, dtype)
-    return dist_util.restated(rainbow_loss_torch, [*tensors, *scalars],
+    return dist_util.restated(rainbow_loss_torch, [*tensors, *scalars, b],
                               {"dvalue": 0, "dadvantage": 1})
+
+
+# ---- generated cases (dist_util.LOSS_SHAPES / ACT_SHAPES) ----------------------------------------
+HEADS = ("value", "advantage", "value_next_online", "advantage_next_online", "value_next_target",
+         "advantage_next_target")
+N_STEP = 3
+
+
+def projected_index(z: dict) -> torch.Tensor:
+    """The projected index b [B, N] of case or fixture `z`, formed once in f32 in the reference's
+    op order: r + (f32(gamma ** n_step) * z) * (1 - d), clamp, - v_min, / f32(delta_z). It is a
+    function of the inputs alone; the kernel's header promises the same per-op rounding. The
+    (l == b) rule is discontinuous in b (at a clamped row f32 gives N - 1 exactly and keeps the
+    row's mass, f64 on the f32 delta_z gives N - 1 + eps and drops it), so the f32 restatement
+    and the f64 twin both take this b and differ only downstream of it."""
+    t = lambda k: torch.from_numpy(z[k]).float()  # noqa: E731
+    support, B = t("support"), z["rewards"].shape[0]
+    gamma_n = float(z["gamma"]) ** int(z["n_step"])
+    v_min, v_max = float(z["v_min"]), float(z["v_max"])
+    next_atoms = t("rewards").view(B, 1) + gamma_n * support * (1 - t("dones").view(B, 1))
+    return (next_atoms.clamp(v_min, v_max) - v_min) / ((v_max - v_min) / (support.numel() - 1))
+
+
+def expected_q(value, advantage, support, A: int, dtype) -> torch.Tensor:
+    """(dueling_dist(value, advantage) * support).sum(2) in `dtype`."""
+    return (dueling_dist(value.to(dtype), advantage.to(dtype), A, support.numel())
+            * support.to(dtype)).sum(2)
+
+
+def make_case(B: int, A: int, N: int, seed: int) -> dict:
+    """Seeded inputs of the Rainbow loss at (B, A, N), with dist_util.plant_edges' rows; PER
+    weights in [0.05, 1] with one exact 1."""
+    rng = dist_util.case_rng("rainbow", (B, A, N), seed)
+    z = {k: dist_util.randn2(rng, B, N if k.startswith("value") else A * N) for k in HEADS}
+    weights = (0.05 + 0.95 * rng.random(B)).astype(f32)
+    weights[rng.integers(0, B)] = 1.0
+    z.update(support=torch.linspace(dist_util.V_MIN, dist_util.V_MAX, N).numpy(), weights=weights,
+             **dist_util.transitions(rng, B, A), gamma=dist_util.GAMMA, n_step=N_STEP,
+             gamma_eff=dist_util.GAMMA ** N_STEP, v_min=dist_util.V_MIN, v_max=dist_util.V_MAX)
+
+    def index_of(r):  # the f32 index of a `done` row with reward r
+        row = dict(z, rewards=np.array([r], f32), dones=np.ones(1, f32))
+        return projected_index(row)[0, 0]
+
+    dist_util.plant_edges(z, N, index_of)
+    return z
+
+
+def with_refs(z: dict) -> dict:
+    """Case `z` with its shared f32 index b, the f32 restatement and the f64 twin on that b, and
+    the twin's expected values of the online net's next-state actions (the double-Q choice)."""
+    b = projected_index(z)
+    N = z["support"].size
+    t = lambda k: torch.from_numpy(z[k])  # noqa: E731
+    q64 = expected_q(t("value_next_online"), t("advantage_next_online"), t("support"),
+                     z["advantage"].shape[1] // N, torch.float64).numpy()
+    return dict(z=z, b=b.numpy(), r32=restated(z, torch.float32, b),
+                r64=restated(z, torch.float64, b), q64=q64)
+
+
+@functools.lru_cache(maxsize=None)
+def loss_case(B: int, A: int, N: int) -> dict:
+    """The generated case at (B, A, N), made once per session and shared; callers must not
+    modify the arrays."""
+    return with_refs(make_case(B, A, N, dist_util.CASE_SEED))
+
+
+@functools.lru_cache(maxsize=None)
+def act_case(E: int, A: int, N: int) -> dict:
+    """Seeded head outputs of the acting kernel at (E, A, N) as CPU tensors, with the expected
+    values in f32 and f64 (numpy); shared, callers must not modify them."""
+    rng = dist_util.case_rng("rainbow_act", (E, A, N), dist_util.CASE_SEED)
+    value = torch.from_numpy(dist_util.randn2(rng, E, N))
+    advantage = torch.from_numpy(dist_util.randn2(rng, E, A * N))
+    support = torch.linspace(dist_util.V_MIN, dist_util.V_MAX, N)
+    return dict(value=value, advantage=advantage, support=support,
+                q32=expected_q(value, advantage, support, A, torch.float32).numpy(),
+                q64=expected_q(value, advantage, support, A, torch.float64).numpy())
