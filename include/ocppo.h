@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCPPO_ABI_VERSION 32
+#define OCPPO_ABI_VERSION 33
 
 /* status codes */
 #define OCPPO_OK 0
@@ -1188,6 +1188,45 @@ OCPPO_API int ocppo_mha_fwd(ocppo_stream_t stream, const float* qkv, const uint8
 OCPPO_API int ocppo_mha_bwd(ocppo_stream_t stream, const float* qkv, const uint8_t* key_valid,
                             const float* out, const float* lse, const float* dout, int64_t B,
                             int64_t S, int64_t E, int64_t heads, float* dqkv);
+
+/* ---------------------------------------------------------------------------------------------
+ * Counter-based dropout for the fused encoder block (ABI 33). No mask tensor exists: every launch
+ * regenerates its mask from
+ *   rng   : device i64 [2] = (seed, offset), read by the kernel (a replayed graph reads the state
+ *           of that replay); ocppo_philox_advance does rng[1] += 1 (one thread)
+ *   site  : host integer in [0, 256); the agent uses 4 * layer + {0 attention probabilities,
+ *           1 dropout1, 2 the FFN's inner dropout, 3 dropout2}
+ *   thr   : host u32 = min((uint64)(p * 2^32), 2^32 - 1); keep iff word >= thr (integer compare)
+ *   scale : 1 / (1 - p), computed in double on the host, passed as f32 (>= 1, finite)
+ * The 32-bit word of an element is a component of Philox4x32-10 with
+ *   counter = (lo32 blk, hi32 blk, lo32 sub, hi32 sub), key = (lo32 seed, hi32 seed),
+ *   sub = offset * 256 + site (mod 2^64), and
+ *   elementwise tensors : flat index e -> blk = e >> 2, component e & 3
+ *   attention probabilities of (sample b, head h, query i, key j), j the absolute key index :
+ *                         blk = ((b * heads + h) * 64 + i) * 16 + (j >> 2), component j & 3
+ * This is a stream of this library, not torch's dropout stream.
+ *
+ * ocppo_dropout: y[e] = keep(e) ? x[e] * scale : 0 for e < n; out of place (x != y); its backward
+ *   is the same call on dy. 16-byte accesses when x and y are 16-B aligned, element by element
+ *   otherwise and for the last n % 4 elements -- the same words either way. n = 0 launches nothing.
+ * ocppo_mha_dropout_fwd / _bwd: ocppo_mha_fwd / _bwd (same contract, same lse) with dropout on
+ *   the attention probabilities: softmax over all valid keys, then out_i = sum_j m_ij P_ij V_j with
+ *   m_ij = keep_ij * scale. A query row whose keys are all dropped yields zeros. Backward:
+ *   dP_ij = m_ij (dO_i . V_j), D_i = dO_i . O_i, dS_ij = P_ij (dP_ij - D_i),
+ *   dV_j = sum_i m_ij P_ij dO_i; every element of dqkv written, excluded keys' dK / dV exactly 0.
+ * ------------------------------------------------------------------------------------------- */
+OCPPO_API int ocppo_dropout(ocppo_stream_t stream, const float* x, const int64_t* rng,
+                            int64_t site, uint32_t thr, float scale, int64_t n, float* y);
+OCPPO_API int ocppo_philox_advance(ocppo_stream_t stream, int64_t* rng);
+OCPPO_API int ocppo_mha_dropout_fwd(ocppo_stream_t stream, const float* qkv,
+                                    const uint8_t* key_valid, const int64_t* rng, int64_t site,
+                                    uint32_t thr, float scale, int64_t B, int64_t S, int64_t E,
+                                    int64_t heads, float* out, float* lse);
+OCPPO_API int ocppo_mha_dropout_bwd(ocppo_stream_t stream, const float* qkv,
+                                    const uint8_t* key_valid, const float* out, const float* lse,
+                                    const float* dout, const int64_t* rng, int64_t site,
+                                    uint32_t thr, float scale, int64_t B, int64_t S, int64_t E,
+                                    int64_t heads, float* dqkv);
 
 /* ---------------------------------------------------------------------------------------------
  * ocppo_add_layernorm_fwd: y = LayerNorm(x + res) * gamma + beta over the last dimension (the

@@ -22,7 +22,7 @@ LIB_PATH = Path(os.environ.get("OCPPO_LIB", PKG / "lib" / "libocppo_hip.so"))
 HEADER = PKG.parent / "include" / "ocppo.h"
 
 # constants mirrored from include/ocppo.h (checked against the header by tests/test_abi.py)
-OCPPO_ABI_VERSION = 32
+OCPPO_ABI_VERSION = 33
 OCPPO_OK, OCPPO_E_INVALID, OCPPO_E_LAUNCH, OCPPO_E_WORKSPACE = 0, 1, 2, 3
 OCPPO_F32, OCPPO_BF16, OCPPO_U8 = 0, 1, 2
 OCPPO_X6_MBITS_ROWS = 2
@@ -32,6 +32,7 @@ OCPPO_NUM_STATS = len(STAT_NAMES)
 
 P, I64, U64, D, I, SZ = (ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_double,
                          ctypes.c_int, ctypes.c_size_t)
+U32, F = ctypes.c_uint32, ctypes.c_float
 
 SIGNATURES: dict[str, tuple[type, list]] = {
     "ocppo_abi_version": (I, []),
@@ -145,6 +146,10 @@ SIGNATURES: dict[str, tuple[type, list]] = {
                                          P, P, P, P, P, I64, I64, I64]),
     "ocppo_mha_fwd": (I, [P, P, P, I64, I64, I64, I64, P, P]),
     "ocppo_mha_bwd": (I, [P, P, P, P, P, P, I64, I64, I64, I64, P]),
+    "ocppo_dropout": (I, [P, P, P, I64, U32, F, I64, P]),
+    "ocppo_philox_advance": (I, [P, P]),
+    "ocppo_mha_dropout_fwd": (I, [P, P, P, P, I64, U32, F, I64, I64, I64, I64, P, P]),
+    "ocppo_mha_dropout_bwd": (I, [P, P, P, P, P, P, P, I64, U32, F, I64, I64, I64, I64, P]),
     "ocppo_add_layernorm_fwd": (I, [P, P, P, P, P, I64, I64, D, P, P, P]),
     "ocppo_add_layernorm_workspace_bytes": (SZ, [I64, I64]),
     "ocppo_add_layernorm_bwd": (I, [P, P, P, P, P, P, P, I64, I64, P, P, P, P, SZ]),

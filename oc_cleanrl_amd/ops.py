@@ -2818,9 +2818,143 @@ class _MHA(torch.autograd.Function):
         return mha_bwd(qkv, key_valid, out, lse, g.contiguous(), ctx.heads), None, None
 
 
-def mha(qkv, key_valid, heads: int):
-    """Differentiable mha_fwd: [B, S, 3E] -> [B, S, E] (the heads concatenated, for out_proj)."""
-    return _MHA.apply(qkv, key_valid, heads)
+# ---- counter-based dropout (include/ocppo.h, ABI 33) ---------------------------
+# The dropout contract of the attention kernels: every head dim of MHA_HEAD_DIMS (the dh = 64
+# backward instantiation compiles to 256 VGPRs without scratch, as the p = 0 one does).
+MHA_DROPOUT_HEAD_DIMS = MHA_HEAD_DIMS
+DROPOUT_SITES = 256
+
+
+def mha_dropout_shape_ok(S: int, E: int, heads: int) -> bool:
+    """The contract of ocppo_mha_dropout_fwd / ocppo_mha_dropout_bwd."""
+    return mha_shape_ok(S, E, heads) and E // heads in MHA_DROPOUT_HEAD_DIMS
+
+
+def dropout_consts(p: float):
+    """(thr, scale) of a drop probability: keep iff word >= thr = min(int(p * 2^32), 2^32 - 1);
+    scale = 1 / (1 - p) in double (the entry points take it as f32)."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dropout: p = {p} not in [0, 1)")
+    return min(int(p * 2 ** 32), 2 ** 32 - 1), 1.0 / (1.0 - p)
+
+
+def _drop_args(rng, site: int, p: float, dev, who: str):
+    """(rng pointer, site, thr, scale) of a launch that draws a mask."""
+    thr, scale = dropout_consts(p)
+    if isinstance(site, bool) or not isinstance(site, int) or not 0 <= site < DROPOUT_SITES:
+        raise ValueError(f"{who}: site {site!r} not an integer in [0, {DROPOUT_SITES})")
+    if rng is None:
+        raise ValueError(f"{who}: p = {p} > 0 needs the generator state rng (i64 [seed, offset])")
+    return _check(rng, "rng", torch.int64, dev, 2), site, thr, scale
+
+
+def philox_state(seed: int, device, offset: int = 0):
+    """A dropout generator state: device i64 [seed, offset]."""
+    return torch.tensor([int(seed), int(offset)], dtype=torch.int64, device=device)
+
+
+def philox_advance(rng):
+    """rng[1] += 1 on the device (one thread; graph-capturable)."""
+    dev = rng.device
+    call("ocppo_philox_advance", _stream(dev), _check(rng, "rng", torch.int64, dev, 2))
+    return rng
+
+
+def dropout_fwd(x, rng, site: int, p: float, out=None):
+    """y = keep ? x / (1 - p) : 0 with the mask of (rng, site) over x's flat index; out of place.
+    The backward is the same call on dy."""
+    dev, f = x.device, torch.float32
+    rp, site, thr, scale = _drop_args(rng, site, p, dev, "dropout")
+    xp = _check(x, "x", f, dev)
+    out = torch.empty_like(x) if out is None else out
+    call("ocppo_dropout", _stream(dev), xp, rp, site, thr, scale, x.numel(),
+         _check(out, "out", f, dev, x.numel()))
+    return out
+
+
+class _Dropout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, rng, site: int, p: float):
+        ctx.save_for_backward(rng)
+        ctx.site, ctx.p = site, p
+        return dropout_fwd(x.detach().contiguous(), rng, site, p)
+
+    @staticmethod
+    def backward(ctx, g):
+        (rng,) = ctx.saved_tensors
+        return dropout_fwd(g.contiguous(), rng, ctx.site, ctx.p), None, None, None
+
+
+def dropout(x, rng, site: int, p: float):
+    """Differentiable counter-based dropout; the backward regenerates the mask from the SAME rng
+    tensor (give every site of one forward a snapshot of the live state). p == 0 launches nothing
+    and returns x."""
+    dropout_consts(p)
+    if p == 0:
+        return x
+    _drop_args(rng, site, p, x.device, "dropout")
+    return _Dropout.apply(x, rng, site, float(p))
+
+
+def _mha_dropout_shape(qkv, key_valid, heads: int, who: str):
+    B, S, E, kv = _mha_shape(qkv, key_valid, heads, who)
+    if not mha_dropout_shape_ok(S, E, heads):
+        raise ValueError(f"{who}: unsupported S={S} E={E} heads={heads} (mha_dropout_shape_ok)")
+    return B, S, E, kv
+
+
+def mha_dropout_fwd(qkv, key_valid, heads: int, rng, site: int, p: float, out=None, lse=None):
+    """mha_fwd with dropout p on the attention probabilities (mask of (rng, site); lse unchanged)."""
+    B, S, E, kv = _mha_dropout_shape(qkv, key_valid, heads, "mha_dropout_fwd")
+    dev, f = qkv.device, torch.float32
+    rp, site, thr, scale = _drop_args(rng, site, p, dev, "mha_dropout_fwd")
+    out = torch.empty((B, S, E), dtype=f, device=dev) if out is None else out
+    lse = torch.empty((B, heads, S), dtype=f, device=dev) if lse is None else lse
+    call("ocppo_mha_dropout_fwd", _stream(dev), _check(qkv, "qkv", f, dev), kv, rp, site, thr,
+         scale, B, S, E, heads, _check(out, "out", f, dev, B * S * E),
+         _check(lse, "lse", f, dev, B * heads * S))
+    return out, lse
+
+
+def mha_dropout_bwd(qkv, key_valid, out, lse, dout, heads: int, rng, site: int, p: float,
+                    dqkv=None):
+    """d qkv of mha_dropout_fwd at the same (rng, site, p)."""
+    B, S, E, kv = _mha_dropout_shape(qkv, key_valid, heads, "mha_dropout_bwd")
+    dev, f = qkv.device, torch.float32
+    rp, site, thr, scale = _drop_args(rng, site, p, dev, "mha_dropout_bwd")
+    dqkv = torch.empty_like(qkv) if dqkv is None else dqkv
+    call("ocppo_mha_dropout_bwd", _stream(dev), _check(qkv, "qkv", f, dev), kv,
+         _check(out, "out", f, dev, B * S * E), _check(lse, "lse", f, dev, B * heads * S),
+         _check(dout, "dout", f, dev, B * S * E), rp, site, thr, scale, B, S, E, heads,
+         _check(dqkv, "dqkv", f, dev, B * S * 3 * E))
+    return dqkv
+
+
+class _MHADropout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, key_valid, heads: int, rng, site: int, p: float):
+        qkv = qkv.detach().contiguous()
+        out, lse = mha_dropout_fwd(qkv, key_valid, heads, rng, site, p)
+        ctx.save_for_backward(qkv, key_valid, out, lse, rng)
+        ctx.heads, ctx.site, ctx.p = heads, site, p
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        qkv, key_valid, out, lse, rng = ctx.saved_tensors
+        return (mha_dropout_bwd(qkv, key_valid, out, lse, g.contiguous(), ctx.heads, rng,
+                                ctx.site, ctx.p), None, None, None, None, None)
+
+
+def mha(qkv, key_valid, heads: int, rng=None, site: int = 0, p: float = 0.0):
+    """Differentiable mha_fwd: [B, S, 3E] -> [B, S, E] (the heads concatenated, for out_proj).
+    p > 0: dropout on the attention probabilities with the mask of (rng, site); the backward
+    reads the same rng tensor. p == 0 is the path without dropout, whatever rng is."""
+    dropout_consts(p)
+    if p == 0:
+        return _MHA.apply(qkv, key_valid, heads)
+    return _MHADropout.apply(qkv, key_valid, heads, rng, site, float(p))
 
 
 def _ln_shape(x, res, weight, who: str):

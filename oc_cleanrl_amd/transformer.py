@@ -16,9 +16,18 @@ runs a block as
 with the four Linears on agents.linear_act (rows = B * S: x6 / hipBLASLt / the rows kernel) and
 the attention core one HIP launch per direction (csrc/ocppo_attn.hip); the residual add +
 LayerNorm has a HIP kernel too (ops.add_layernorm), routed to torch's ops where it measured
-slower (ADD_LAYERNORM_HIP). That path needs `dropout == 0` (in-kernel dropout is not built): with the
-reference's default dropout = 0.1 every block runs torch's own layer modules. `--dropout 0`
-selects the fused path; `FUSED_ATTN = False` turns it off (tests, tools/bench_transformer.py).
+slower (ADD_LAYERNORM_HIP). By default that path needs `dropout == 0`: with the reference's
+default dropout = 0.1 every block runs torch's own layer modules. `--dropout 0` selects the fused
+path; `FUSED_ATTN = False` turns it off (tests, tools/bench_transformer.py).
+
+`--fused-dropout` puts `dropout > 0` on the fused path too: the four dropout sites of a layer
+(attention probabilities inside ops.mha; dropout1, the FFN's inner dropout and dropout2 on
+ops.dropout) draw counter-based masks from the agent's own generator state `rng` = device i64
+(seed, offset) -- a documented Philox stream, NOT torch's dropout stream. One
+forward snapshots the state, every site of that forward and of its backward reads the snapshot,
+and the forward ends by advancing the live state by one; all of it is graph-capturable. As with
+torch's modules (and the reference, which never calls eval()), dropout is active iff
+`self.training`.
 
 The trainer's `(buffer_window_size, num_features)` observation is read as (S objects, F
 features); `num_obj` stands in for the reference's `envs.get_attr("num_obj")`. Host envs
@@ -90,6 +99,8 @@ def _fields():
         if f.name not in names and f.name not in _SKIP:
             out.append((f.name, f.type, _OWN_DEFAULTS.get(f.name, f.default)))
     out.append(("num_obj", int, 3))  # leading object-type columns (envs.get_attr("num_obj"))
+    # dropout > 0 on the fused block path with counter-based masks (off: torch's layer modules)
+    out.append(("fused_dropout", bool, False))
     return [(n, t, dataclasses.field(default=d)) for n, t, d in out]
 
 
@@ -129,17 +140,21 @@ def finalize(args, world_size: int = 1):
     return args
 
 
-def attn_shape_ok(S: int, E: int, num_heads: int, dropout: float) -> bool:
-    """The kernel contract (1 <= S <= 64, head dim in {8, 16, 32, 64}, E <= 512) and no dropout."""
-    return dropout == 0 and ops.mha_shape_ok(S, E, num_heads)
+def attn_shape_ok(S: int, E: int, num_heads: int, dropout: float,
+                  fused_dropout: bool = False) -> bool:
+    """The kernel contract (1 <= S <= 64, head dim in {8, 16, 32, 64}, E <= 512) and no dropout;
+    with fused_dropout, 0 < dropout < 1 too, within the dropout kernels' contract."""
+    if dropout == 0:
+        return ops.mha_shape_ok(S, E, num_heads)
+    return bool(fused_dropout) and 0 < dropout < 1 and ops.mha_dropout_shape_ok(S, E, num_heads)
 
 
-def attn_ok(x, emb_dim: int, num_heads: int, dropout: float) -> bool:
+def attn_ok(x, emb_dim: int, num_heads: int, dropout: float, fused_dropout: bool = False) -> bool:
     """The fused block path applies to the object sets x [B, S, F]: a GPU f32 contiguous input,
     attn_shape_ok for its tokens [B, S, emb_dim], and the module switch."""
     return (FUSED_ATTN and isinstance(x, torch.Tensor) and x.dim() == 3 and x.is_cuda and
             x.dtype == torch.float32 and x.is_contiguous() and x.shape[0] >= 1 and
-            attn_shape_ok(x.shape[1], emb_dim, num_heads, dropout))
+            attn_shape_ok(x.shape[1], emb_dim, num_heads, dropout, fused_dropout))
 
 
 def pool(h, mask, pooling_type: str):
@@ -171,7 +186,7 @@ class OCTransformerAgent(_ActorCritic):
     grads_in_place = False
 
     def __init__(self, envs, emb_dim, num_heads, num_blocks, masking, num_obj, device=None,
-                 pooling_type="max", num_post_layers=1, dropout=0.1):
+                 pooling_type="max", num_post_layers=1, dropout=0.1, fused_dropout=False, seed=0):
         super().__init__()
         if pooling_type not in POOLING_TYPES:
             raise NotImplementedError(pooling_type)
@@ -179,6 +194,9 @@ class OCTransformerAgent(_ActorCritic):
         dims = envs.observation_space.shape
         self.num_obj, self.masking, self.pooling_type = num_obj, bool(masking), pooling_type
         self.num_heads, self.dropout = num_heads, float(dropout)
+        # fused_dropout: dropout > 0 on the fused path. rng = device i64 (seed, offset), made on
+        # the first input's device; a plain attribute (the state-dict keys stay the reference's)
+        self.fused_dropout, self.seed, self.rng = bool(fused_dropout), int(seed), None
         encoder_layer = TransformerEncoderLayer(emb_dim, num_heads, emb_dim, device=device,
                                                 dropout=dropout, batch_first=True)
         self.encoder = nn.Linear(dims[1], emb_dim, device=device)
@@ -195,30 +213,49 @@ class OCTransformerAgent(_ActorCritic):
         return x[..., :self.num_obj].sum(dim=-1, dtype=bool)
 
     @staticmethod
-    def _block(layer, x2, B: int, S: int, key_valid):
-        """One TransformerEncoderLayer (post-norm, ReLU, no dropout) on tokens x2 [B * S, E]."""
+    def _block(layer, x2, B: int, S: int, key_valid, rng=None, site0: int = 0, p: float = 0.0):
+        """One TransformerEncoderLayer (post-norm, ReLU) on tokens x2 [B * S, E]. p > 0: dropout
+        at its four sites, masks of (rng, site0 + {0 attention probabilities, 1 dropout1, 2 the
+        FFN's inner dropout, 3 dropout2})."""
         sa = layer.self_attn
         E = x2.shape[1]
         in_proj = SimpleNamespace(weight=sa.in_proj_weight, bias=sa.in_proj_bias)
         qkv = linear_act(x2, in_proj, False)
-        a = ops.mha(qkv.view(B, S, 3 * E), key_valid, sa.num_heads)
+        if p == 0:
+            a = ops.mha(qkv.view(B, S, 3 * E), key_valid, sa.num_heads)
+        else:
+            a = ops.mha(qkv.view(B, S, 3 * E), key_valid, sa.num_heads, rng, site0, p)
         a = linear_act(a.view(B * S, E), sa.out_proj, False)
-        x2 = _add_norm(x2, a, layer.norm1)
-        f = linear_act(linear_act(x2, layer.linear1, True), layer.linear2, False)
-        return _add_norm(x2, f, layer.norm2)
+        x2 = _add_norm(x2, ops.dropout(a, rng, site0 + 1, p), layer.norm1)
+        f = ops.dropout(linear_act(x2, layer.linear1, True), rng, site0 + 2, p)
+        f = linear_act(f, layer.linear2, False)
+        return _add_norm(x2, ops.dropout(f, rng, site0 + 3, p), layer.norm2)
 
     def tokens(self, x, mask):
         """transformer(encoder(x)) [B, S, E] (:260 / :238-242): the fused block path when attn_ok,
-        else torch's modules."""
+        else torch's modules. With fused_dropout and dropout > 0 in train(): one snapshot of the
+        generator state serves every site of this forward and of its backward, and the live state
+        moves on by one at the end (a backward that runs after later forwards still regenerates
+        its own forward's masks)."""
         B, S, _ = x.shape
         E = self.encoder.out_features
-        if not attn_ok(x, E, self.num_heads, self.dropout):
+        if not attn_ok(x, E, self.num_heads, self.dropout, self.fused_dropout):
             pad = None if mask is None else ~mask
             return self.transformer(self.encoder(x), src_key_padding_mask=pad), False
+        p = self.dropout if self.training else 0.0
+        snap = None
+        if p > 0:
+            if 4 * len(self.transformer.layers) > ops.DROPOUT_SITES:
+                raise ValueError("fused dropout numbers its sites 4 * layer + k < 256")
+            if self.rng is None or self.rng.device != x.device:
+                self.rng = ops.philox_state(self.seed, x.device)
+            snap = self.rng.clone()
         kv = None if mask is None else mask.to(torch.uint8).contiguous()
         h = linear_act(x.reshape(B * S, x.shape[2]), self.encoder, False)
-        for layer in self.transformer.layers:
-            h = self._block(layer, h, B, S, kv)
+        for i, layer in enumerate(self.transformer.layers):
+            h = self._block(layer, h, B, S, kv, snap, 4 * i, p)
+        if p > 0:
+            ops.philox_advance(self.rng)
         return h.view(B, S, E), True
 
     def trunk(self, x, prescaled: bool = False):
@@ -251,7 +288,7 @@ class TransformerTrainer(PPOTrainer):
         return OCTransformerAgent(EnvSpec(self.obs_shape, self.A), a.emb_dim, a.num_heads,
                                   a.num_blocks, a.masking, a.num_obj, None,
                                   pooling_type=a.pooling_type, num_post_layers=a.num_post_layers,
-                                  dropout=a.dropout)
+                                  dropout=a.dropout, fused_dropout=a.fused_dropout, seed=a.seed)
 
 
 def run_transformer(args, device=None) -> TransformerTrainer:
