@@ -15,6 +15,7 @@ actions are bit-identical to the reference's under the same seed.
 """
 from __future__ import annotations
 
+import itertools
 import threading
 
 import numpy as np
@@ -891,7 +892,7 @@ def _conv_x6(x, conv, relu: bool):
             y._ocppo_cbox = box
         return y
     B, Cin, H, _ = x.shape
-    wp = (_planes_infer(conv.weight) if CONV_ROWS_PLANES and _IN_ROLLOUT[0] and
+    wp = (_planes_infer(conv.weight) if CONV_ROWS_PLANES and _in_rollout() and
           not torch.is_grad_enabled() else None)
     return ops.timed(f"conv_x6_{B}x{Cin}x{H}_{conv.out_channels}",
                      lambda: ops.conv_x6(x, conv.weight, conv.bias, s, relu, w_planes=wp))
@@ -903,24 +904,20 @@ def _conv_x6(x, conv, relu: bool):
 # 21.2 / 16.1 us: the planes' 6 B per element against 4, read straight from L2 without an LDS
 # stage; tools/exp_conv_rows.py, profiles/r06/config3/rows/), so off
 CONV_ROWS_PLANES = False
-_PLANES_INFER: dict = {}
 
 
 def _planes_infer(w):
     """bf16 [3, Cout, KH KW C] pieces of a channels_last conv weight's [Cout, KH KW C] matrix,
     refreshed once per rollout (rollout_inference); None when the weight is not channels_last."""
-    ent = _PLANES_INFER.get(id(w))
-    if ent is None or ent[0] is not w:
-        wm = w.permute(0, 2, 3, 1).reshape(w.shape[0], -1)
+    def make():
+        # (detached: the splitter hangs on w, so it must not hold w itself through a view's base)
+        wm = w.detach().permute(0, 2, 3, 1).reshape(w.shape[0], -1)
         if wm.data_ptr() != w.data_ptr() or not wm.is_contiguous() or wm.shape[1] % 8:
             return None
-        wp = ops.WeightPlanes(fwd=(wm,))
-        ent = [w, wp, wm._ocppo_planes["fwd"], -1]
-        _PLANES_INFER[id(w)] = ent
-    if ent[3] != _WEIGHTS_GEN[0]:
-        ent[1].refresh()
-        ent[3] = _WEIGHTS_GEN[0]
-    return ent[2]
+        return ops.WeightPlanes(fwd=(wm,))
+
+    wp = _rollout_form(w, "planes", make, ops.WeightPlanes.refresh)
+    return None if wp is None else wp.jobs[0][2]
 
 
 def _conv_act_ok(x, conv) -> bool:
@@ -1040,28 +1037,55 @@ def linear_act_nhwc(x, lin: nn.Linear, relu: bool):
 # with the weight's columns permuted to match, instead of nn.Flatten's NCHW-order copy of the
 # activation every step (3.2 MB, one ~6 us launch per step). The permuted weight is made once per
 # rollout, inside rollout_inference() only (the trainer's rollout: the parameters cannot change
-# within it; entering it marks the cache stale, and the copy rides in the first step, captured
-# with the rollout graph), and reused by the other steps.
+# within it; entering it marks the weight's rollout forms stale, and the copy rides in the first
+# step, captured with the rollout graph), and reused by the other steps.
 FLAT_NHWC_INFER = True
-_NHWC_INFER: dict = {}
-_WEIGHTS_GEN = [0]
-_IN_ROLLOUT = [False]
+
+
+class _RolloutScope(threading.local):
+    depth = 0  # open rollout_inference scopes of this thread
+    gen = 0    # the outermost one's generation: unique in the process, growing
+
+
+_ROLLOUT = _RolloutScope()
 
 
 class rollout_inference:
-    """Context of one rollout (trainer._rollout): the parameters are fixed inside it, so the
-    inference caches (linear_act_nhwc_infer's permuted weight) are valid; refreshed on entry."""
+    """Context of one rollout (trainer._rollout): the parameters are fixed inside it, so their
+    rollout forms (_rollout_form) are valid once refilled. Per thread, like weight_planes(), and
+    nestable: only the outermost entry starts a new generation."""
+    _generations = itertools.count(1)
 
     def __enter__(self):
-        _WEIGHTS_GEN[0] += 1
-        _IN_ROLLOUT[0] = True
+        if _ROLLOUT.depth == 0:
+            _ROLLOUT.gen = next(self._generations)
+        _ROLLOUT.depth += 1
+        return self
 
     def __exit__(self, *exc):
-        _IN_ROLLOUT[0] = False
+        _ROLLOUT.depth -= 1
+
+
+def _in_rollout() -> bool:
+    return _ROLLOUT.depth > 0
+
+
+def _rollout_form(w, kind: str, make, fill):
+    """Parameter w's derived tensor `kind` for the rollout, kept on the parameter
+    (w._ocppo_rollout[kind], freed with it): make() allocates it once, so its address never
+    changes (the rollout graph holds it); fill(form) refills it from w on first use in each
+    outermost rollout_inference scope. None, and never filled, when make() returns None."""
+    ent = w.__dict__.setdefault("_ocppo_rollout", {}).get(kind)
+    if ent is None:
+        ent = w._ocppo_rollout[kind] = [make(), None]
+    if ent[1] != _ROLLOUT.gen and ent[0] is not None:
+        fill(ent[0])
+        ent[1] = _ROLLOUT.gen
+    return ent[0]
 
 
 def _flat_nhwc_infer_ok(x, flat, lin) -> bool:
-    return (FLAT_NHWC_INFER and _IN_ROLLOUT[0] and not torch.is_grad_enabled()
+    return (FLAT_NHWC_INFER and _in_rollout() and not torch.is_grad_enabled()
             and isinstance(flat, nn.Flatten)
             and isinstance(lin, nn.Linear) and lin.bias is not None and x.is_cuda
             and x.dtype == torch.float32 and x.dim() == 4 and flat.start_dim == 1
@@ -1069,40 +1093,28 @@ def _flat_nhwc_infer_ok(x, flat, lin) -> bool:
             and not x.is_contiguous() and lin.in_features == x[0].numel())
 
 
-_CONTIG_INFER: dict = {}
-
-
 def _contig_infer(w):
     """A contiguous copy of parameter w, refreshed once per rollout (rollout_inference)."""
-    ent = _CONTIG_INFER.get(id(w))
-    if ent is None or ent[0] is not w:
-        ent = [w, torch.empty(w.shape, dtype=w.dtype, device=w.device), -1]
-        _CONTIG_INFER[id(w)] = ent
-    if ent[2] != _WEIGHTS_GEN[0]:
-        ent[1].copy_(w)
-        ent[2] = _WEIGHTS_GEN[0]
-    return ent[1]
+    return _rollout_form(w, "contig",
+                         lambda: torch.empty(w.shape, dtype=w.dtype, device=w.device),
+                         lambda t: t.copy_(w))
 
 
 def linear_act_nhwc_infer(x, lin: nn.Linear, relu: bool):
     """act(lin(flatten(x))) without autograd for a channels_last x, reading x in its memory order
-    against a cached column-permuted weight (same products, columns visited in (H, W, C) order)."""
+    against the weight's column-permuted rollout form (same products, columns visited in (H, W, C)
+    order)."""
     B, C, H, W = x.shape
-    key = id(lin)
-    ent = _NHWC_INFER.get(key)
-    if ent is None or ent[0] is not lin.weight:
-        ent = [lin.weight, torch.empty_like(lin.weight), -1]
-        _NHWC_INFER[key] = ent
-    if ent[2] != _WEIGHTS_GEN[0]:
-        ent[1].copy_(_cols_to_nhwc(lin.weight, (C, H, W)))
-        ent[2] = _WEIGHTS_GEN[0]
+    w = lin.weight
+    wn = _rollout_form(w, "nhwc", lambda: torch.empty_like(w),
+                       lambda t: t.copy_(_cols_to_nhwc(w, (C, H, W))))
     x2 = x.permute(0, 2, 3, 1).reshape(B, H * W * C)
     if HIP_FLAT_INFER:
         return ops.timed(f"linear_act_{B}x{lin.out_features}x{H * W * C}",
-                         lambda: ops.linear_act(x2, ent[1], lin.bias, relu))
+                         lambda: ops.linear_act(x2, wn, lin.bias, relu))
     if relu:
-        return torch._addmm_activation(lin.bias, x2, ent[1].t(), use_gelu=False)
-    return torch.addmm(lin.bias, x2, ent[1].t())
+        return torch._addmm_activation(lin.bias, x2, wn.t(), use_gelu=False)
+    return torch.addmm(lin.bias, x2, wn.t())
 
 
 # ... on the HIP f32-MFMA rows kernel (ops.linear_act: 16 x 16 output tiles, K split over 8 waves,
@@ -1230,7 +1242,7 @@ class _ActorCritic(Predictor):
         relu = isinstance(net[1], nn.ReLU)
         box = {"bias": conv.bias} if relu and CONV_DGRAD_RELU else None
         # the rollout (weights fixed): the weight's tap-order copy made once per rollout
-        wn = (_contig_infer(conv.weight) if _IN_ROLLOUT[0] and not torch.is_grad_enabled()
+        wn = (_contig_infer(conv.weight) if _in_rollout() and not torch.is_grad_enabled()
               and not conv.weight.is_contiguous() else None)
         y = _ConvX6U8.apply(conv.weight, conv.bias, frames, idx, conv.stride[0], relu, div, box,
                             wn)

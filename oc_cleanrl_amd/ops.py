@@ -10,6 +10,7 @@ Reference lines replaced are cited per function (paths relative to the reference
 from __future__ import annotations
 
 import ctypes
+import functools
 
 import torch
 
@@ -80,6 +81,28 @@ def _stream(device: torch.device) -> int:
     if device.type != "cuda":
         raise ValueError(f"HIP kernels need GPU tensors, got device {device} (no CPU fallback)")
     return torch.cuda.current_stream(device).cuda_stream
+
+
+# Every per-shape workspace of this module (split-K partials, ticket and flag words, index
+# tables), by (tag, device, key). A (tag, device, key) is allocated at most once per process and
+# never freed or resized: captured hipGraphs hold the pointer. The launches of one stream share a
+# buffer (they run one after another); trainers on different streams share it too.
+_PERSISTENT: dict = {}
+
+
+def _persistent(tag: str, dev, key, make):
+    """The buffer `make()` returned the first time (tag, dev, key) was asked for. tag: the owning
+    entry point's name, so two entry points never share one; dev: any spelling of a device (the
+    key holds it with an explicit index: "cuda" and "cuda:0" are one GPU)."""
+    buf = _PERSISTENT.get((tag, dev, key))  # a tensor's .device is in the key's form already
+    if buf is None:
+        dev = torch.device(dev)
+        if dev.index is None:
+            dev = torch.device(dev.type, torch.cuda.current_device() if dev.type == "cuda" else 0)
+        buf = _PERSISTENT.get((tag, dev, key))
+        if buf is None:
+            buf = _PERSISTENT[(tag, dev, key)] = make()
+    return buf
 
 
 # ---------------------------------------------------------------------------------------------
@@ -246,9 +269,6 @@ def ppo_loss_fwd_bwd(logits, new_value, b_actions, b_logprobs, b_advantages, b_r
     return stats, dlogits, dvalue
 
 
-_HL_WS: dict = {}
-
-
 # decoder widths ocppo_heads_loss_fwd_bwd is instantiated for (H / 64 columns per lane: 1, 2, 4, 8)
 HEADS_LOSS_WIDTHS = (64, 128, 256, 512)
 
@@ -300,11 +320,8 @@ def heads_loss_fwd_bwd(h, wa, ba, wc, bc, mb_actions, mb_logprobs, mb_advantages
     dba = torch.empty(A, dtype=f, device=dev) if dba is None else dba
     dbc = torch.empty(1, dtype=f, device=dev) if dbc is None else dbc
     stats = torch.empty(len(STAT_NAMES), dtype=f, device=dev) if stats is None else stats
-    key = (dev, M, H, A)
-    ws = _HL_WS.get(key)
-    if ws is None:
-        nb = int(_lib.LIB.ocppo_heads_loss_workspace_bytes(M, H, A))
-        ws = _HL_WS[key] = torch.zeros(nb // 4, dtype=f, device=dev)
+    ws = _persistent("heads_loss_fwd_bwd", dev, (M, H, A), lambda: torch.zeros(
+        int(_lib.LIB.ocppo_heads_loss_workspace_bytes(M, H, A)) // 4, dtype=f, device=dev))
     call("ocppo_heads_loss_rows" if defer is not None else "ocppo_heads_loss_fwd_bwd",
          _stream(dev), _check(h, "h", f, dev, M * H), M, H,
          _check(wa, "wa", f, dev, A * H), _check(ba, "ba", f, dev, A), _check(wc, "wc", f, dev, H),
@@ -749,7 +766,6 @@ def conv_x6_ok(x, weight, stride: int, wgrad: bool = False, dgrad: bool = False)
     return True
 
 
-_CONV_PARTS: dict = {}
 # weight gradients: K splits for about this many workgroups (each split's partial [Cout, N] summed
 # in split order by the same launch's sum_parts), per tile; measured at config 3's minibatch of
 # 8192 (profiles/r05/ab_conv_wgrad_units.txt): 32 x 128 (the first layer) and 64 x 128 best at
@@ -771,7 +787,6 @@ def _geom(*v):
 # is handed the extents of the sources its gathers read, from the pointers it is passed, and a
 # device record of the first out-of-range index (tests/test_conv_bounds_gpu.py reads it).
 X6_BOUNDS = hasattr(_lib.LIB, "ocppo_x6_probe_set_bounds")
-_BOUNDS_REC: dict = {}
 BOUND_KINDS = {1: "f32 source offset", 2: "image index", 3: "u8 stack row", 4: "u8 byte offset"}
 
 
@@ -783,10 +798,14 @@ def _tail(t) -> int:
 def bounds_record(dev) -> torch.Tensor:
     """The bounds-check build's violation record on `dev` (int32 [count, first kind, first index
     lo, hi, its limit lo, hi, 0, 0])."""
-    key = str(dev)
-    if key not in _BOUNDS_REC:
-        _BOUNDS_REC[key] = torch.zeros(8, dtype=torch.int32, device=dev)
-    return _BOUNDS_REC[key]
+    return _persistent("bounds_record", dev, (),
+                       lambda: torch.zeros(8, dtype=torch.int32, device=dev))
+
+
+def __getattr__(name):
+    if name == "_BOUNDS_REC":  # every device's record, by device (the suite's fixture reads it)
+        return {str(k[1]): v for k, v in _PERSISTENT.items() if k[0] == "bounds_record"}
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def _bounds(dev, x=None, u8=None):
@@ -861,10 +880,8 @@ def conv_x6(x, weight, bias=None, stride: int = 1, relu: bool = True, out=None, 
              _opt(mbits, "mbits", torch.int32, dev, M * Cout // 32))
         return out
     # few rows (the rollout's batch): K-split partials, then bias + ReLU on their ordered sum
-    key = ("fwd", str(dev), S, M, Cout)
-    if key not in _CONV_PARTS:
-        _CONV_PARTS[key] = torch.empty((S, M, Cout), dtype=f, device=dev)
-    part = _CONV_PARTS[key]
+    part = _persistent("conv_x6", dev, (S, M, Cout),
+                       lambda: torch.empty((S, M, Cout), dtype=f, device=dev))
     call("ocppo_conv_x6", _stream(dev), 0, x.data_ptr(), geom, wm.data_ptr(), K, part.data_ptr(),
          Cout, M, Cout, K, S, None, 0, None, tile, None, None, None, None, wpp, None)
     call("ocppo_sum_splits_act", _stream(dev), part.data_ptr(), S, M, Cout,
@@ -918,10 +935,8 @@ def conv_x6_wgrad(gp, x, kernel: tuple, stride: int, out=None):
     bm, bn = _CONV_TILES[tile]
     tiles = (Cout // bm) * (N // bn)
     S = max(1, min(rows // 32 // 32, _wgrad_units(tile) // tiles))
-    key = ("wgrad", str(dev), S, Cout, N)
-    if key not in _CONV_PARTS:
-        _CONV_PARTS[key] = torch.empty((S, Cout, N), dtype=f, device=dev)
-    part = _CONV_PARTS[key]
+    part = _persistent("conv_x6_wgrad", dev, (S, Cout, N),
+                       lambda: torch.empty((S, Cout, N), dtype=f, device=dev))
     if out is None:
         out = torch.empty((Cout, N), dtype=f, device=dev)
     if out.numel() != Cout * N or not out.is_contiguous(memory_format=torch.channels_last
@@ -1005,8 +1020,6 @@ def conv_x6_dgrad(gp, weight, stride: int, in_hw: tuple, out=None, relu_out=None
     return out
 
 
-_DG_IDX: dict = {}
-_DG_BUF: dict = {}
 # the data gradients' B operand (the stride classes' flipped weights) pre-split into bf16 planes
 # once per call (ocppo_split_planes) instead of in every workgroup of the product
 CONV_DGRAD_PLANES = True
@@ -1018,23 +1031,23 @@ CONV_DGRAD_PLANES_128 = True
 def _dgrad_weight(weight, s: int, planes: bool = False):
     """(wc, its bf16 planes or None): conv_x6_dgrad's B operand [s s C, T TW Cout], row (py, px,
     c), column (t, tw, co) = weight[co, c, py + s (T - 1 - t), px + s (TW - 1 - tw)], gathered in
-    one launch into a buffer kept per weight (and split into planes by one more)."""
+    one launch into a buffer the weight owns (weight._ocppo_dgrad[s]: its own, freed with it; and
+    split into planes by one more launch)."""
     Cout, C, KH, KW = weight.shape
     mem = weight.permute(0, 2, 3, 1)  # a view of the memory when channels_last
-    key = (str(weight.device), Cout, C, KH, KW, s)
-    idx = _DG_IDX.get(key)
-    if idx is None:
+    dev = weight.device
+
+    def make_idx():
         ar = torch.arange(Cout * KH * KW * C).view(Cout, KH, KW, C).permute(0, 3, 1, 2)
         idx = torch.stack([ar[:, :, py::s, px::s].flip(2, 3).permute(1, 2, 3, 0)
                            for py in range(s) for px in range(s)])
-        idx = idx.reshape(s * s * C, -1).to(weight.device)
-        _DG_IDX[key] = idx
-    bkey = key + (weight.data_ptr(),)
-    ent = _DG_BUF.get(bkey)
+        return idx.reshape(s * s * C, -1).to(dev)
+
+    idx = _persistent("_dgrad_weight", dev, (Cout, C, KH, KW, s), make_idx)
+    own = weight.__dict__.setdefault("_ocppo_dgrad", {})
+    ent = own.get(s)
     if ent is None:
-        buf = torch.empty(idx.shape, dtype=torch.float32, device=weight.device)
-        ent = [buf, None]
-        _DG_BUF[bkey] = ent
+        ent = own[s] = [torch.empty(idx.shape, dtype=torch.float32, device=dev), None]
     buf = ent[0]
     with torch.no_grad():  # (the kernel timer replays this outside autograd's backward)
         torch.index_select(mem.reshape(-1), 0, idx.view(-1), out=buf.view(-1))
@@ -1142,13 +1155,11 @@ def conv_x6_u8(src, idx, weight, bias=None, stride: int = 4, relu: bool = True,
 # stack in LDS once, rewritten per channel as tap-column rows; 4 partials per workgroup summed in
 # order) for NatureCNN's first layer on 4 x 84 x 84 stacks
 CONV_U8_IMG_WGRAD = True
-_CUS: dict = {}
 
 
+@functools.lru_cache(maxsize=None)
 def _cus(dev) -> int:
-    if str(dev) not in _CUS:
-        _CUS[str(dev)] = torch.cuda.get_device_properties(dev).multi_processor_count
-    return _CUS[str(dev)]
+    return torch.cuda.get_device_properties(dev).multi_processor_count
 
 
 def _conv_u8_img_wgrad_ok(src, kernel, stride: int, Cout: int) -> bool:
@@ -1182,18 +1193,14 @@ def conv_x6_u8_wgrad(gp, src, idx, kernel: tuple, stride: int = 4, divisor: floa
         if rows != B * OH * OW:
             raise ValueError("conv_x6_u8_wgrad: gp must be [B OH OW, Cout]")
         S = 4 * min(_cus(dev), B)  # 4 wave partials per workgroup, <= one workgroup per image
-        key = ("wgrad_img", str(dev), S, Cout, N)
-        if key not in _CONV_PARTS:
-            _CONV_PARTS[key] = torch.empty((S, Cout, N), dtype=f, device=dev)
-        part = _CONV_PARTS[key]
+        part = _persistent("conv_x6_u8_wgrad.img", dev, (S, Cout, N),
+                           lambda: torch.empty((S, Cout, N), dtype=f, device=dev))
         if out is None:
             out = torch.empty((Cout, N), dtype=f, device=dev)
         dbp = None
         if db is not None:
-            dkey = ("wgrad_img_db", str(dev), S, Cout)
-            if dkey not in _CONV_PARTS:
-                _CONV_PARTS[dkey] = torch.empty((S, Cout), dtype=f, device=dev)
-            dbp = _CONV_PARTS[dkey].data_ptr()
+            dbp = _persistent("conv_x6_u8_wgrad.img_db", dev, (S, Cout),
+                              lambda: torch.empty((S, Cout), dtype=f, device=dev)).data_ptr()
         _bounds(dev, u8=src)
         call("ocppo_conv_x6_u8", _stream(dev), 1, src.data_ptr(),
              _check(idx, "idx", torch.int64, dev, B), C, H, W, KH, KW, s,
@@ -1206,10 +1213,8 @@ def conv_x6_u8_wgrad(gp, src, idx, kernel: tuple, stride: int = 4, divisor: floa
         raise ValueError("conv_x6_u8_wgrad: gp must be [B OH OW, Cout] with a tile for it")
     bm, bn = _CONV_TILES[tile]
     S = max(1, min(rows // 32 // 32, _wgrad_units(tile) // ((Cout // bm) * (N // bn))))
-    key = ("wgrad", str(dev), S, Cout, N)
-    if key not in _CONV_PARTS:
-        _CONV_PARTS[key] = torch.empty((S, Cout, N), dtype=f, device=dev)
-    part = _CONV_PARTS[key]
+    part = _persistent("conv_x6_u8_wgrad", dev, (S, Cout, N),
+                       lambda: torch.empty((S, Cout, N), dtype=f, device=dev))
     if out is None:
         out = torch.empty((Cout, N), dtype=f, device=dev)
     _bounds(dev, u8=src)
@@ -1380,18 +1385,10 @@ def head_env_store_linear2(hidden, w_actor, b_actor, w_critic, b_critic, noise, 
 # Linear(+ReLU) backward, elementwise part: threshold_backward + bias sum in one pass
 # (autograd of architectures/ppo.py:60-84 inside ppo_atari_oc.py:605)
 # ---------------------------------------------------------------------------------------------
-_RB_WS: dict = {}
-
-
 def _relu_bias_ws(R: int, N: int, dev):
-    """Per-shape workspace (tickets zeroed once, then self re-arming); never reallocated, so
-    captured graphs keep valid pointers."""
-    key = (dev, R, N)
-    ws = _RB_WS.get(key)
-    if ws is None:
-        nb = int(_lib.LIB.ocppo_relu_bias_grad_workspace_bytes(R, N))
-        ws = _RB_WS[key] = torch.zeros(nb, dtype=torch.uint8, device=dev)
-    return ws
+    """relu_bias_grad's tickets (zeroed once, then self re-arming)."""
+    return _persistent("relu_bias_grad", dev, (R, N), lambda: torch.zeros(
+        int(_lib.LIB.ocppo_relu_bias_grad_workspace_bytes(R, N)), dtype=torch.uint8, device=dev))
 
 
 def relu_bias_grad_ok(g) -> bool:
@@ -1426,23 +1423,20 @@ def relu_bias_grad(g, out=None, db=None, gp=None, bits=None):
     return (gp if out is not None else g), db
 
 
-_RB_PART: dict = {}
-
-
 def relu_bias_grad_partial(g, out=None, gp=None):
     """(gp, (partials, chunks)): relu_bias_grad with the bias-gradient chunk sums left for
     sum_splits_db (deferred to the launch that combines the layer's split-K weight gradient).
-    partials [chunks, N] f32 is a per-shape persistent buffer (graph-safe)."""
+    partials [chunks, N] f32 is a per-shape persistent buffer (_persistent)."""
     R, N = g.shape
     dev = g.device
     f = torch.float32
     if out is not None and gp is None:
         gp = torch.empty_like(g)
-    key = (dev, R, N)
-    buf = _RB_PART.get(key)
-    if buf is None:
+    def make():
         chunks = int(_lib.LIB.ocppo_relu_bias_grad_chunks(R, N))
-        buf = _RB_PART[key] = (torch.zeros((chunks, N), dtype=f, device=dev), chunks)
+        return torch.zeros((chunks, N), dtype=f, device=dev), chunks
+
+    buf = _persistent("relu_bias_grad_partial", dev, (R, N), make)
     call("ocppo_relu_bias_grad_partial", _stream(dev), _check(g, "g", f, dev),
          _opt(out, "out", f, dev, R * N), _opt(gp, "gp", f, dev, R * N), buf[0].data_ptr(), R, N)
     return (gp if out is not None else g), buf
@@ -1496,11 +1490,9 @@ def relu_bias_wgrad(g, out, x, dw=None, db=None, defer=None):
         db = torch.empty(N, dtype=f, device=dev)
     if tuple(dw.shape) != (N, K) or not dw.is_contiguous():
         raise ValueError(f"dw must be a contiguous [{N}, {K}] tensor")
-    key = (dev, "wg", R, N, K)
-    ws = _RB_WS.get(key)
-    if ws is None:
-        nb = int(_lib.LIB.ocppo_relu_bias_wgrad_workspace_bytes(R, N, K))
-        ws = _RB_WS[key] = torch.zeros(nb, dtype=torch.uint8, device=dev)
+    ws = _persistent("relu_bias_wgrad", dev, (R, N, K), lambda: torch.zeros(
+        int(_lib.LIB.ocppo_relu_bias_wgrad_workspace_bytes(R, N, K)), dtype=torch.uint8,
+        device=dev))
     call("ocppo_relu_bias_wgrad_rows" if defer is not None else "ocppo_relu_bias_wgrad",
          _stream(dev), _check(g, "g", f, dev),
          _opt(out, "out", f, dev, R * N),
@@ -1539,11 +1531,8 @@ def heads_bwd(h, dlogits, dvalue, wa, wc, relu: bool = True, gp=None, db_h=None,
         dbc = torch.empty(1, dtype=f, device=dev) if dbc is None else dbc
     else:
         dwc = dbc = None
-    key = (dev, "hb", M, H, A)
-    ws = _RB_WS.get(key)
-    if ws is None:
-        nb = int(_lib.LIB.ocppo_heads_bwd_workspace_bytes(M, H, A))
-        ws = _RB_WS[key] = torch.zeros(nb, dtype=torch.uint8, device=dev)
+    ws = _persistent("heads_bwd", dev, (M, H, A), lambda: torch.zeros(
+        int(_lib.LIB.ocppo_heads_bwd_workspace_bytes(M, H, A)), dtype=torch.uint8, device=dev))
     call("ocppo_heads_bwd", _stream(dev), _check(h, "h", f, dev, M * H),
          _check(dlogits, "dlogits", f, dev, M * A), _opt(dvalue, "dvalue", f, dev, M),
          _check(wa, "wa", f, dev, A * H), _opt(wc, "wc", f, dev, H),
@@ -1671,19 +1660,16 @@ def _x6_operand_ok(t) -> bool:
             and t.stride(1) == 1 and t.stride(0) % 4 == 0)
 
 
-_SK_WS: dict = {}
-
-
 def x6_sk_workspace(tile: int, device):
     """The stream-K workspace of a pipelined tile on `device` (zeroed once; every launch leaves
-    its flags at zero again). Shared by the launches of one stream: they run one after another."""
-    key = (tile, str(device))
-    if key not in _SK_WS:
+    its flags at zero again)."""
+    def make():
         n = _lib.LIB.ocppo_gemm_x6_sk_workspace_bytes(tile)
         if n == 0:
             raise ValueError(f"gemm_x6: tile {tile} has no stream-K form")
-        _SK_WS[key] = torch.zeros(n, dtype=torch.uint8, device=device)
-    return _SK_WS[key]
+        return torch.zeros(n, dtype=torch.uint8, device=device)
+
+    return _persistent("x6_sk_workspace", device, tile, make)
 
 
 def x6_mbits_words(M: int, N: int, tile: int) -> int:
@@ -1854,9 +1840,6 @@ def dx_x6(g, w, out=None, planes=None, tile=None):
                    b_planes=planes, tile=tile)
 
 
-_WG_REC = {}
-
-
 def dx_x6_wgrad_ok(g, w, mask, x) -> bool:
     """dX = g W with the lower layer's backward in the epilogue (dx_x6_wgrad) applies."""
     M, N = g.shape
@@ -1881,10 +1864,8 @@ def dx_x6_wgrad(g, w, mask, x, dw, db, defer, tile=27):
     bm = 64 if tile == 27 else 128
     kp = 4 if K1 <= 4 else 8 if K1 <= 8 else 12 if K1 <= 12 else 16
     nrec = (M // bm) * ((K + 255) // 256) * 256 * (kp + 1)
-    key = (dev, M, K, kp, tile)
-    rec = _WG_REC.get(key)
-    if rec is None:
-        rec = _WG_REC[key] = torch.empty(nrec, dtype=torch.float32, device=dev)
+    rec = _persistent("dx_x6_wgrad", dev, (M, K, kp, tile),
+                      lambda: torch.empty(nrec, dtype=torch.float32, device=dev))
     f = torch.float32
     args = (g.data_ptr(), g.stride(0), 1, w.data_ptr(), 1, w.stride(0), M, K, N,
             mask.data_ptr(), mask.stride(0), x.data_ptr(), x.stride(0), K1,
@@ -2104,16 +2085,13 @@ def frames_scatter(dh, uniq, inv, mb: int, dones, T: int, N: int, W: int, out=No
     return out
 
 
-_SCATTER_DBP: dict = {}
-
-
 def frames_scatter_relu(dh, uniq, inv, mb: int, dones, T: int, N: int, W: int, out=None,
                         gp=None, with_db: bool = True, mbits=None):
     """frames_scatter with the ReLU backward of the layer whose output `out` [C, E] encoded the
     frames: gp = out <= 0 ? 0 : denc (ocppo_frames_scatter_relu). mbits: that output's row-major
     ReLU bitmask (linear_x6(..., mbits="rows")), read instead of `out`. Returns (gp, (partials,
     chunks)): the bias-gradient chunk sums (16 frames per chunk; a per-shape persistent buffer,
-    graph-safe) for sum_splits_db, or (gp, None) without with_db."""
+    _persistent) for sum_splits_db, or (gp, None) without with_db."""
     M = dh.shape[0]
     E = dh.shape[-1]
     if dh.numel() != M * W * E:
@@ -2125,11 +2103,11 @@ def frames_scatter_relu(dh, uniq, inv, mb: int, dones, T: int, N: int, W: int, o
         gp = torch.empty((C, E), dtype=f, device=dev)
     part = None
     if with_db:
-        key = (dev, C, E)
-        part = _SCATTER_DBP.get(key)
-        if part is None:
+        def make():
             chunks = int(_lib.LIB.ocppo_frames_scatter_chunks(C))
-            part = _SCATTER_DBP[key] = (torch.zeros((chunks, E), dtype=f, device=dev), chunks)
+            return torch.zeros((chunks, E), dtype=f, device=dev), chunks
+
+        part = _persistent("frames_scatter_relu", dev, (C, E), make)
     call("ocppo_frames_scatter_relu", _stream(dev), _check(dh, "dh", f, dev), M, E,
          _check(uniq, "uniq", torch.int32, dev), C, _check(inv, "inv", torch.int32, dev, T * N),
          int(mb), _check(dones, "dones", f, dev, (T + 1) * N), T, N, W,

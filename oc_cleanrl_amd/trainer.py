@@ -145,16 +145,11 @@ def rank_seeds(seed: int, rank: int) -> tuple[int, int]:
     return seed, seed + rank
 
 
-_SCRUB: dict = {}
-
-
 def l3_scrub(device, mib: int = 640):
     """A launch that streams `mib` MiB through the caches (a sum over a resident buffer, 2.5x the
     256 MiB Infinity Cache): whatever a kernel read before it is no longer cached after it."""
-    key = (str(device), mib)
-    if key not in _SCRUB:
-        _SCRUB[key] = torch.ones(mib << 18, dtype=torch.float32, device=device)
-    buf = _SCRUB[key]
+    buf = ops._persistent("l3_scrub", device, mib, lambda: torch.ones(
+        mib << 18, dtype=torch.float32, device=device))
     return lambda: buf.sum()
 
 

@@ -116,6 +116,50 @@ def test_data_gradient(name, pad_copy, monkeypatch):
     assert torch.equal(dx, ops.conv_x6_dgrad(gp, w, s, (H, H)))
 
 
+def test_data_gradient_class_weights_belong_to_their_weight():
+    """ops._dgrad_weight: the gathered class weights hang on the weight they were gathered from
+    (weight._ocppo_dgrad[stride]) -- two live weights of one shape get two buffers, each bitwise
+    the index_select of its own weight, the data gradient of each is what it is with the other
+    weight absent, and a weight's buffer goes when the weight does."""
+    import gc
+    import weakref
+
+    x, w1, _, s = _operands("conv2", 3)
+    _, w2, _, _ = _operands("conv2", 7)
+    Cout, C, K, _ = w1.shape
+    H = x.shape[2]
+    OH = (H - K) // s + 1
+    g = torch.Generator(device=DEV).manual_seed(4)
+    gp = (torch.rand(x.shape[0], Cout, OH, OH, device=DEV, generator=g) * 2 - 1
+          ).contiguous(memory_format=CL)
+    alone = [ops.conv_x6_dgrad(gp, w.clone(memory_format=torch.preserve_format), s, (H, H))
+             for w in (w1, w2)]
+    dx1 = ops.conv_x6_dgrad(gp, w1, s, (H, H))
+    dx2 = ops.conv_x6_dgrad(gp, w2, s, (H, H))
+    dx1b = ops.conv_x6_dgrad(gp, w1, s, (H, H))
+    assert torch.equal(dx1, alone[0]) and torch.equal(dx2, alone[1]) and torch.equal(dx1b, dx1)
+    assert not torch.equal(dx1, dx2)
+    w64, gp64 = w1.double().cpu(), gp.double().cpu()
+    _check(dx1, torch.nn.grad.conv2d_input(x.shape, w64, gp64, stride=s),
+           torch.nn.grad.conv2d_input(x.shape, w64.abs(), gp64.abs(), stride=s),
+           torch.nn.grad.conv2d_input(x.shape, w1, gp, stride=s))
+    b1, b2 = w1._ocppo_dgrad[s][0], w2._ocppo_dgrad[s][0]
+    assert b1 is not b2 and b1.data_ptr() != b2.data_ptr()
+    # row (py, px, c), column (t, tw, co) = weight[co, c, py + s (T - 1 - t), px + s (TW - 1 - tw)]
+    idx = ops._persistent("_dgrad_weight", DEV, (Cout, C, K, K, s), None)
+    for w, b in ((w1, b1), (w2, b2)):
+        mem = w.permute(0, 2, 3, 1).reshape(-1)
+        assert torch.equal(b.view(-1), torch.index_select(mem, 0, idx.view(-1)))
+        T = K // s
+        cls = torch.stack([w[:, :, py::s, px::s].flip(2, 3).permute(1, 2, 3, 0)
+                           for py in range(s) for px in range(s)]).reshape(s * s * C, T * T * Cout)
+        assert torch.equal(b, cls)
+    ref = weakref.ref(b1)
+    del b1, w1, w, b, mem
+    gc.collect()
+    assert ref() is None and w2._ocppo_dgrad[s][0] is b2
+
+
 def test_config3_minibatch_shapes_are_taken():
     """Every layer of config 3's update (minibatch 8192) and rollout (256 envs) forward fits."""
     for B in (8192, 256):

@@ -878,7 +878,9 @@ def test_rollout_flatten_linear_reads_the_nhwc_activation(dev):
         ref = ag.trunk(x)
         with agents.rollout_inference():
             got = ag.trunk(x)
-            assert any(k == id(m) for k in agents._NHWC_INFER for m in ag.network)
+        # the Flatten's successor Linear: its weight carries the rollout form
+        assert any("nhwc" in getattr(m.weight, "_ocppo_rollout", {}) for m in ag.network
+                   if isinstance(m, torch.nn.Linear))
         torch.testing.assert_close(got, ref, rtol=1e-5, atol=1e-5)
         lin = [m for m in ag.network if isinstance(m, torch.nn.Linear)][0]
         lin.weight.mul_(0.5)  # an update between rollouts (in place, as FlatAdam's)
@@ -887,6 +889,91 @@ def test_rollout_flatten_linear_reads_the_nhwc_activation(dev):
             got2 = ag.trunk(x)
         torch.testing.assert_close(got2, ref2, rtol=1e-5, atol=1e-5)
         assert not torch.allclose(ref2, ref)
+
+
+def _nature_trunk_operands(dev, seed):
+    from oc_cleanrl_amd.agents import make_agent
+
+    torch.manual_seed(seed)
+    ag = make_agent("PPO", (4, 84, 84), 4, dev).to(dev).to(memory_format=torch.channels_last)
+    x = torch.randint(0, 256, (256, 4, 84, 84), device=dev).float().contiguous(
+        memory_format=torch.channels_last)
+    lin = [m for m in ag.network if isinstance(m, torch.nn.Linear)][0]
+    return ag, x, lin
+
+
+def test_rollout_forms_belong_to_their_parameter(dev):
+    """A weight's rollout form (agents._rollout_form) hangs on the weight: two agents get two,
+    and nothing in the package keeps one alive once its agent is gone."""
+    import gc
+    import weakref
+
+    from oc_cleanrl_amd import agents
+
+    a, x, lin_a = _nature_trunk_operands(dev, 0)
+    b, _, lin_b = _nature_trunk_operands(dev, 1)
+    with torch.no_grad():
+        for ag in (a, b):
+            with agents.rollout_inference():
+                ag.trunk(x)
+    fa = lin_a.weight._ocppo_rollout["nhwc"][0]
+    fb = lin_b.weight._ocppo_rollout["nhwc"][0]
+    assert fa is not fb and fa.data_ptr() != fb.data_ptr()
+    assert fa.shape == lin_a.weight.shape and not torch.equal(fa, fb)
+    ref = weakref.ref(fa)
+    del fa, lin_a, a, ag
+    gc.collect()
+    assert ref() is None
+    assert lin_b.weight._ocppo_rollout["nhwc"][0] is fb
+
+
+def test_rollout_forms_keep_their_address_across_rollouts(dev):
+    """The rollout graph holds a form's pointer: every rollout refills the same tensor in place,
+    and the output follows the weights' in-place updates between rollouts -- the Flatten Linear's
+    permuted weight (trunk) and the first convolution's tap-order copy (trunk_frames: the same
+    first-layer bits in and out of the scope, then the same Flatten Linear difference)."""
+    from oc_cleanrl_amd import agents
+
+    ag, x, lin = _nature_trunk_operands(dev, 0)
+    conv = [m for m in ag.network if isinstance(m, torch.nn.Conv2d)][0]
+    frames = x.to(torch.uint8).contiguous()
+    idx = torch.arange(frames.shape[0], device=dev)
+    assert ag.trunk_frames_ok(frames, idx.numel())
+    ptrs, outs = [], []
+    with torch.no_grad():
+        for _ in range(3):
+            ref, ref_u8 = ag.trunk(x), ag.trunk_frames(frames, idx)
+            with agents.rollout_inference():
+                got, got_u8 = ag.trunk(x), ag.trunk_frames(frames, idx)
+            torch.testing.assert_close(got, ref, rtol=1e-5, atol=1e-5)
+            torch.testing.assert_close(got_u8, ref_u8, rtol=1e-5, atol=1e-5)
+            ptrs.append({(n, k): e[0].data_ptr() for n, p in ag.named_parameters()
+                         for k, e in getattr(p, "_ocppo_rollout", {}).items()})
+            outs.append((ref, ref_u8))
+            lin.weight.mul_(0.5)  # an update between rollouts (in place, as FlatAdam's)
+            conv.weight.mul_(0.5)
+    assert sorted(k for _, k in ptrs[0]) == ["contig", "nhwc"]
+    assert ptrs[0] == ptrs[1] == ptrs[2]
+    for i in (0, 1):
+        assert not torch.allclose(outs[i][0], outs[i + 1][0])
+        assert not torch.allclose(outs[i][1], outs[i + 1][1])
+
+
+def test_pixel_rollout_graph_replay_is_bitwise_eager(dev):
+    """The pixel trainer's captured rollout refills the weights' rollout forms inside the graph
+    (the refresh copies are captured with step 0): three iterations with hipGraphs leave bitwise
+    the parameters of three eager ones."""
+    runs = []
+    for graphs in (False, True):
+        args = small_args(env_id="ALE/Breakout-v5", obs_mode="dqn", architecture="PPO",
+                          num_envs=256, num_steps=8, update_epochs=1, cuda_graphs=graphs)
+        tr, _ = run_iters(args, 3, dev)
+        assert tr.graphs_ready == graphs
+        runs.append(tr)
+    a, b = runs
+    assert torch.equal(a.actions, b.actions)
+    for (n, p), q in zip(a.agent.named_parameters(), b.agent.parameters()):
+        assert torch.equal(p, q), n
 
 
 def test_conv_relu_backward_in_the_flattened_linear_dx(dev, monkeypatch):
