@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCPPO_ABI_VERSION 33
+#define OCPPO_ABI_VERSION 34
 
 /* status codes */
 #define OCPPO_OK 0
@@ -1250,6 +1250,51 @@ OCPPO_API int ocppo_add_layernorm_bwd(ocppo_stream_t stream, const float* dy, co
                                       const float* rstd, int64_t R, int64_t E, float* dx,
                                       float* dgamma, float* dbeta, void* workspace,
                                       size_t workspace_bytes);
+
+/* ---------------------------------------------------------------------------------------------
+ * The recurrent PPO agent's LSTM (cleanrl/ppo_atari_lstm.py:140-158, Agent.get_states: one
+ * single-layer nn.LSTM call per time step with the incoming state multiplied by 1 - done), ABI 34.
+ * All f32; gate order i | f | g | o; w_ih [4H, I], w_hh [4H, H], b_ih, b_hh [4H] as nn.LSTM stores
+ * them. One step, for every environment b on its own:
+ *   h_in = (1 - done[t, b]) * h,   c_in = (1 - done[t, b]) * c
+ *   z = pre[t, b] + h_in w_hh^T + b_hh;   i, f, o = sigmoid(z_i, z_f, z_o), g = tanh(z_g)
+ *   c = f * c_in + i * g,   h = o * tanh(c)
+ * Contract: H in {32, 64, 128}, T >= 1, B (N) >= 1, I >= 1, B < 2^31; a negative size, another H
+ * or a null required pointer returns OCPPO_E_INVALID before any launch; T = 0 or B = 0 (N = 0)
+ * launches nothing. One launch per call, no atomics, no waiting between workgroups (a workgroup
+ * owns whole environments for the whole call); an environment's arithmetic runs in an order fixed
+ * by H alone, so its results do not depend on B or on the other rows. Graph-capturable.
+ *
+ * ocppo_lstm_seq_fwd: the recurrence over a whole sequence.
+ *   pre   : [T, B, 4H] the input projection x w_ih^T + b_ih (one GEMM outside)
+ *   done  : [T, B];  h0, c0 : [B, H];  w_hh 16-byte aligned
+ *   h_out : [T, B, H];  hT, cT : [B, H] the state after step T - 1
+ *   c_out [T, B, H], gates [T, B, 4H] (the ACTIVATED gates), h_in [T, B, H] (the masked state each
+ *   step consumed): what the backward needs; each may be NULL (inference).
+ *   Only rows t < T, b < B of an output are written.
+ *
+ * ocppo_lstm_seq_bwd: its backward through time, t = T - 1 .. 0, carrying (dh, dc).
+ *   dh_out : [T, B, H] the gradient at h_out;  gates, c_out, c0, done, w_hh as above
+ *   dgates : [T, B, 4H] the gradient at the pre-activations z (= d pre; d w_hh = dgates^T h_in and
+ *            d b_hh = its column sum are GEMM-shaped and left to the caller)
+ *   What flows from step t to step t - 1 is multiplied by 1 - done[t]. The initial state and the
+ *   final state carry no gradient (the script passes a detached clone and drops the final state).
+ *
+ * ocppo_lstm_step: one step for the rollout, both products inside: x [N, I], done [N];
+ *   h, c [N, H] updated in place. z = (x w_ih^T + h_in w_hh^T) + (b_ih + b_hh).
+ * ------------------------------------------------------------------------------------------- */
+OCPPO_API int ocppo_lstm_seq_fwd(ocppo_stream_t stream, const float* pre, const float* w_hh,
+                                 const float* b_hh, const float* done, const float* h0,
+                                 const float* c0, int64_t T, int64_t B, int64_t H, float* h_out,
+                                 float* c_out, float* gates, float* h_in, float* hT, float* cT);
+OCPPO_API int ocppo_lstm_seq_bwd(ocppo_stream_t stream, const float* dh_out, const float* gates,
+                                 const float* c_out, const float* c0, const float* done,
+                                 const float* w_hh, int64_t T, int64_t B, int64_t H,
+                                 float* dgates);
+OCPPO_API int ocppo_lstm_step(ocppo_stream_t stream, const float* x, const float* w_ih,
+                              const float* b_ih, const float* w_hh, const float* b_hh,
+                              const float* done, int64_t N, int64_t I, int64_t H, float* h,
+                              float* c);
 
 #ifdef __cplusplus
 }

@@ -22,7 +22,7 @@ LIB_PATH = Path(os.environ.get("OCPPO_LIB", PKG / "lib" / "libocppo_hip.so"))
 HEADER = PKG.parent / "include" / "ocppo.h"
 
 # constants mirrored from include/ocppo.h (checked against the header by tests/test_abi.py)
-OCPPO_ABI_VERSION = 33
+OCPPO_ABI_VERSION = 34
 OCPPO_OK, OCPPO_E_INVALID, OCPPO_E_LAUNCH, OCPPO_E_WORKSPACE = 0, 1, 2, 3
 OCPPO_F32, OCPPO_BF16, OCPPO_U8 = 0, 1, 2
 OCPPO_X6_MBITS_ROWS = 2
@@ -153,6 +153,9 @@ SIGNATURES: dict[str, tuple[type, list]] = {
     "ocppo_add_layernorm_fwd": (I, [P, P, P, P, P, I64, I64, D, P, P, P]),
     "ocppo_add_layernorm_workspace_bytes": (SZ, [I64, I64]),
     "ocppo_add_layernorm_bwd": (I, [P, P, P, P, P, P, P, I64, I64, P, P, P, P, SZ]),
+    "ocppo_lstm_seq_fwd": (I, [P, P, P, P, P, P, P, I64, I64, I64, P, P, P, P, P, P]),
+    "ocppo_lstm_seq_bwd": (I, [P, P, P, P, P, P, P, I64, I64, I64, P]),
+    "ocppo_lstm_step": (I, [P, P, P, P, P, P, P, I64, I64, I64, P, P]),
 }
 
 

@@ -944,7 +944,7 @@ HIP_ROLLOUT_CONV = True
 def _hip_conv_ok(x, conv) -> bool:
     return (HIP_ROLLOUT_CONV and not torch.is_grad_enabled() and
             not torch.backends.cudnn.benchmark and _conv_act_ok(x, conv) and
-            conv.in_channels <= 4 and conv.in_channels & (conv.in_channels - 1) == 0 and
+            conv.in_channels == 4 and  # ocppo_conv2d_act: Cin a power of two >= 4 (1 frame: MIOpen)
             conv.padding == (0, 0) and conv.stride[0] == conv.stride[1] and x.shape[0] <= 1024
             and (conv.kernel_size[0] * conv.kernel_size[1] * conv.in_channels) % 16 == 0)
 

@@ -2992,3 +2992,137 @@ class _AddLayerNorm(torch.autograd.Function):
 def add_layernorm(x, res, weight, bias, eps: float = 1e-5):
     """Differentiable LayerNorm(x + res) * weight + bias (the post-norm step of an encoder block)."""
     return _AddLayerNorm.apply(x, res, weight, bias, eps)
+
+
+# ---------------------------------------------------------------------------------------------
+# the recurrent agent's LSTM (ppo_atari_lstm.py:140-158: one nn.LSTM call per step, state * (1 - done))
+# ---------------------------------------------------------------------------------------------
+LSTM_HIDDEN = (32, 64, 128)
+
+
+def lstm_shape_ok(T: int, B: int, I: int, H: int) -> bool:
+    """The contract of ocppo_lstm_seq_fwd / _bwd / ocppo_lstm_step."""
+    return T >= 1 and B >= 1 and I >= 1 and H in LSTM_HIDDEN
+
+
+def _lstm_shape(pre, w_hh, who: str):
+    if pre.dim() != 3 or pre.shape[2] % 4:
+        raise ValueError(f"{who}: pre must be [T, B, 4H], got {tuple(pre.shape)}")
+    T, B, G = pre.shape
+    if not lstm_shape_ok(T, B, 1, G // 4):
+        raise ValueError(f"{who}: unsupported T={T} B={B} H={G // 4} (lstm_shape_ok)")
+    return T, B, G // 4
+
+
+def lstm_seq_fwd(pre, w_hh, b_hh, done, h0, c0, save: bool = True):
+    """The masked recurrence over pre [T, B, 4H] (= x W_ih^T + b_ih), done [T, B], h0 / c0 [B, H]:
+    (h_out [T, B, H], hT, cT [B, H], saved) with saved = (c_out, gates, h_in) for lstm_seq_bwd, or
+    None (save=False: inference)."""
+    T, B, H = _lstm_shape(pre, w_hh, "lstm_seq_fwd")
+    dev, f = pre.device, torch.float32
+    h_out = torch.empty((T, B, H), dtype=f, device=dev)
+    hT, cT = torch.empty((B, H), dtype=f, device=dev), torch.empty((B, H), dtype=f, device=dev)
+    saved = (torch.empty((T, B, H), dtype=f, device=dev),
+             torch.empty((T, B, 4 * H), dtype=f, device=dev),
+             torch.empty((T, B, H), dtype=f, device=dev)) if save else None
+    call("ocppo_lstm_seq_fwd", _stream(dev), _check(pre, "pre", f, dev),
+         _check(w_hh, "w_hh", f, dev, 4 * H * H), _check(b_hh, "b_hh", f, dev, 4 * H),
+         _check(done, "done", f, dev, T * B), _check(h0, "h0", f, dev, B * H),
+         _check(c0, "c0", f, dev, B * H), T, B, H, h_out.data_ptr(),
+         *((t.data_ptr() for t in saved) if save else (None, None, None)), hT.data_ptr(),
+         cT.data_ptr())
+    return h_out, hT, cT, saved
+
+
+def lstm_seq_bwd(dh_out, gates, c_out, c0, done, w_hh):
+    """dgates [T, B, 4H]: the gradient at the pre-activations (= d pre) of lstm_seq_fwd."""
+    T, B, H = _lstm_shape(gates, w_hh, "lstm_seq_bwd")
+    dev, f = gates.device, torch.float32
+    dgates = torch.empty((T, B, 4 * H), dtype=f, device=dev)
+    call("ocppo_lstm_seq_bwd", _stream(dev), _check(dh_out, "dh_out", f, dev, T * B * H),
+         _check(gates, "gates", f, dev), _check(c_out, "c_out", f, dev, T * B * H),
+         _check(c0, "c0", f, dev, B * H), _check(done, "done", f, dev, T * B),
+         _check(w_hh, "w_hh", f, dev, 4 * H * H), T, B, H, dgates.data_ptr())
+    return dgates
+
+
+def _lstm_dw_splits(T: int) -> int:
+    """Groups of time steps dW_hh = dgates^T h_in is summed over before the groups are added: T
+    itself up to 32 steps, else T's largest divisor <= 32."""
+    return next(s for s in range(min(T, 32), 0, -1) if T % s == 0)
+
+
+class _LSTMSeq(torch.autograd.Function):
+    """h_out, hT, cT of the masked recurrence; backward = ocppo_lstm_seq_bwd (dpre) + the two
+    GEMM-shaped parameter gradients: dW_hh = dgates^T h_in (summed per group of steps), db_hh = the
+    column sum of dgates -- written into the flat gradient buffer in place for FlatAdam-owned
+    parameters, as agents._LinearAct does. The initial state gets no gradient (the script passes a
+    detached clone, ppo_atari_lstm.py:234, 310); hT / cT are not differentiable."""
+
+    @staticmethod
+    def forward(ctx, pre, w_hh, b_hh, done, h0, c0):
+        pre, w, b = pre.detach().contiguous(), w_hh.detach(), b_hh.detach()
+        done, h0, c0 = done.detach().contiguous(), h0.detach().contiguous(), c0.detach().contiguous()
+        h_out, hT, cT, (c_out, gates, h_in) = lstm_seq_fwd(pre, w, b, done, h0, c0)
+        ctx.save_for_backward(gates, c_out, h_in, c0, done, w)
+        ctx.w_hh, ctx.b_hh = w_hh, b_hh
+        ctx.mark_non_differentiable(hT, cT)
+        return h_out, hT, cT
+
+    @staticmethod
+    def backward(ctx, g, _ghT, _gcT):
+        from . import agents  # (agents imports this module)
+
+        gates, c_out, h_in, c0, done, w = ctx.saved_tensors
+        T, B, G = gates.shape
+        dgates = lstm_seq_bwd(g.contiguous(), gates, c_out, c0, done, w)
+        dg2 = dgates.view(T * B, G)
+        dw = db = None
+        if ctx.needs_input_grad[1]:
+            # per group of steps first, then over the groups (one bmm + one sum): autograd's own
+            # accumulation over the steps of the torch loop has this shape, and a single sum over
+            # all T * B rows (agents._weight_grad at these row counts) measured 4x its error
+            # (4.8e-7 against 1.2e-7 of the largest element at T * B = 119, H = 128)
+            out = ctx.w_hh.grad if agents._direct(ctx.w_hh) else None
+            s = _lstm_dw_splits(T)
+            part = torch.bmm(dgates.view(s, T // s * B, G).transpose(1, 2),
+                             h_in.view(s, T // s * B, G // 4))
+            dw = None if out is not None else part.sum(0)
+            if out is not None:
+                torch.sum(part, 0, out=out)
+        if ctx.needs_input_grad[2]:
+            if agents._direct(ctx.b_hh):
+                torch.sum(dg2, 0, out=ctx.b_hh.grad)
+            else:
+                db = dg2.sum(0)
+        return (dgates if ctx.needs_input_grad[0] else None), dw, db, None, None, None
+
+
+def lstm_seq(pre, w_hh, b_hh, done, h0, c0):
+    """(h_out [T, B, H], (hT, cT)) of Agent.get_states' loop (ppo_atari_lstm.py:148-156) on
+    pre = x W_ih^T + b_ih [T, B, 4H]: one launch forward, one backward."""
+    for t, name in ((pre, "pre"), (w_hh, "w_hh"), (b_hh, "b_hh"), (done, "done"), (h0, "h0"),
+                    (c0, "c0")):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise ValueError(f"lstm_seq: {name} must be a GPU tensor (no CPU fallback)")
+    h_out, hT, cT = _LSTMSeq.apply(pre, w_hh, b_hh, done, h0, c0)
+    return h_out, (hT, cT)
+
+
+def lstm_step(x, w_ih, b_ih, w_hh, b_hh, done, h, c):
+    """One rollout step (ppo_atari_lstm.py:248, 268): x [N, I], done [N]; h, c [N, H] updated in
+    place (and returned). One launch, no autograd."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or not isinstance(h, torch.Tensor) or \
+            h.dim() != 2:
+        raise ValueError("lstm_step: x must be [N, I] and h [N, H]")
+    N, I = x.shape
+    H = h.shape[1]
+    dev, f = x.device, torch.float32
+    px = _check(x, "x", f)
+    if h.shape[0] != N or not lstm_shape_ok(1, N, I, H):
+        raise ValueError(f"lstm_step: unsupported N={N} I={I} H={H} (lstm_shape_ok)")
+    call("ocppo_lstm_step", _stream(dev), px, _check(w_ih, "w_ih", f, dev, 4 * H * I),
+         _check(b_ih, "b_ih", f, dev, 4 * H), _check(w_hh, "w_hh", f, dev, 4 * H * H),
+         _check(b_hh, "b_hh", f, dev, 4 * H), _check(done, "done", f, dev, N), N, I, H,
+         _check(h, "h", f, dev, N * H), _check(c, "c", f, dev, N * H))
+    return h, c

@@ -761,18 +761,22 @@ class PPOTrainer:
             # the reference's T per-step draws (the claimed generator range), one launch
             self.timer.bracket("noise_draws", lambda: self.exp_stream.fill(self.noise))
 
+    def _bootstrap_value(self):
+        """The critic's value of the observation after the last step (:533-534); a subclass whose
+        agent carries state between steps overrides it."""
+        T = self.T
+        if self.frame_cache:
+            return self.agent._head(self.agent.critic, self._policy_hidden(T))
+        if self.u8_rollout:
+            return self.agent._head(self.agent.critic,
+                                    self.agent.trunk_frames(self.obs[T], self.env_rows))
+        return self.agent.get_value(self.net_obs, self.prescale)
+
     def _rollout_end(self):
         """Bootstrap + GAE (:533-547) + minibatch adv stats (:577-579)."""
         a = self.args
         T = self.T
-        if self.frame_cache:
-            self.values[T].copy_(self.agent._head(self.agent.critic,
-                                                  self._policy_hidden(T)).view(-1))
-        elif self.u8_rollout:
-            self.values[T].copy_(self.agent._head(
-                self.agent.critic, self.agent.trunk_frames(self.obs[T], self.env_rows)).view(-1))
-        else:
-            self.values[T].copy_(self.agent.get_value(self.net_obs, self.prescale).view(-1))
+        self.values[T].copy_(self._bootstrap_value().view(-1))
         rec = self.records
         self.timer.bracket("gae", lambda: ops.gae(
             self.rewards, self.values[:T], self.dones[:T], self.values[T], self.dones[T],
@@ -859,8 +863,9 @@ class PPOTrainer:
         with agents.weight_planes():
             return self._forward_backward_body(j)
 
-    def _forward_backward_body(self, j: int):
-        a = self.args
+    def _minibatch_hidden(self, j: int):
+        """The heads' input for minibatch j's rows, under autograd (a subclass with layers between
+        the trunk and the heads overrides it)."""
         idx = self.perm_dev[j * self.M:(j + 1) * self.M]
         ag = self.agent
         if self.frame_dedup:
@@ -870,22 +875,21 @@ class PPOTrainer:
                                              idx, k, split=self.split)
             if self.split:
                 hidden, self.cuts[j] = hidden
-            if self._fused_tail(j, hidden):
-                return
-            logits, value = ag.heads(hidden)
-        elif self.u8_first_conv:
+            return hidden
+        if self.u8_first_conv:
             # the first convolution reads the u8 frame stacks through idx (no f32 minibatch copy)
-            hidden = ag.trunk_frames(self.b_obs, idx)
-            if self._fused_tail(j, hidden):
-                return
-            logits, value = ag.heads(hidden)
-        else:
-            self.timer.bracket("gather", lambda: ops.gather_rows(self.b_obs, idx, self.mb_obs,
-                                                                 scale255=self.prescale))
-            hidden = ag.trunk(self.mb_obs, self.prescale)
-            if self._fused_tail(j, hidden):
-                return
-            logits, value = ag.heads(hidden)
+            return ag.trunk_frames(self.b_obs, idx)
+        self.timer.bracket("gather", lambda: ops.gather_rows(self.b_obs, idx, self.mb_obs,
+                                                             scale255=self.prescale))
+        return ag.trunk(self.mb_obs, self.prescale)
+
+    def _forward_backward_body(self, j: int):
+        a = self.args
+        ag = self.agent
+        hidden = self._minibatch_hidden(j)
+        if self._fused_tail(j, hidden):
+            return
+        logits, value = ag.heads(hidden)
         lg, vv = logits.detach(), value.detach().view(-1)  # the timer's closure must not hold
         sl = slice(j * self.M, (j + 1) * self.M)
         mb = self.mb
