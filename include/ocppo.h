@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCPPO_ABI_VERSION 34
+#define OCPPO_ABI_VERSION 35
 
 /* status codes */
 #define OCPPO_OK 0
@@ -1295,6 +1295,75 @@ OCPPO_API int ocppo_lstm_step(ocppo_stream_t stream, const float* x, const float
                               const float* b_ih, const float* w_hh, const float* b_hh,
                               const float* done, int64_t N, int64_t I, int64_t H, float* h,
                               float* c);
+
+/* ---------------------------------------------------------------------------------------------
+ * PQN (cleanrl/pqn_atari_envpool.py) on the device rollout, ABI 35. All f32. A negative size, a
+ * size outside a contract below or a null required pointer returns OCPPO_E_INVALID before any
+ * launch; a zero row / env / sample count launches nothing and returns OCPPO_OK. No atomics:
+ * every result is the same run to run. Graph-capturable.
+ *
+ * ocppo_q_lambda: the Q(lambda) targets of :248-261, bitwise the script's f32 loop (same ops, same
+ * order, no FMA contraction; gamma, q_lambda and 1 - q_lambda rounded to f32 once):
+ *   t = T-1 : returns[t] = rewards[t] + (gamma * max_a next_q) * (1 - next_done)
+ *   t < T-1 : returns[t] = rewards[t] + (gamma * (q_lambda * returns[t+1]
+ *                                                 + (1 - q_lambda) * values[t+1])) * (1 - dones[t+1])
+ *   rewards, values, dones, returns : [T, N];  next_q : [N, A];  next_done : [N];  A >= 1
+ *
+ * ocppo_ln_relu_fwd: y = relu(LayerNorm(x) * gamma + beta) over the last dimension of [R, E] rows,
+ * 1 <= E <= 1024 (relu = 0: no ReLU). mean, rstd [R] are written. The row is centred before the
+ * variance is taken (sum of squared deviations / E, never E[x^2] - mean^2), and re-centred once so
+ * that a common offset of the row costs no precision; rstd = 1 / sqrt(var + eps).
+ * ocppo_ln_relu_bwd: dx [R, E], dgamma, dbeta [E] from dy, x, y (the ReLU mask is y > 0; y may be
+ * NULL with relu = 0), mean and rstd. Per-workgroup partials of dgamma / dbeta (a grid that
+ * depends on R only) go to the workspace (ocppo_ln_relu_workspace_bytes(R, E)) with plain stores
+ * and are summed in workgroup order by a second launch of the same call.
+ *
+ * ocppo_pqn_act: q = hidden wq^T + bq for hidden [N, H], wq [A, H]; values[n] = max_a q[n, a] at
+ * the LOWEST index among equal maxima (torch.argmax on the CPU), actions[n] = that index or, with
+ * probability epsilon, a uniform random action: exactly ocppo_epsilon_greedy's schedule, coin and
+ * random action for the same (seed, *step + step_offset). epsilon_out [1] and q_out [N, A] may be
+ * NULL. Contract: 1 <= A <= 18, H a multiple of 4 in [4, 1024], hidden and wq 16-byte aligned
+ * (ocppo_q_head_epsilon_greedy's, widened), duration > 0.
+ *
+ * ocppo_pqn_loss_fwd_bwd: F.mse_loss(returns, q[b, actions[b]]) of :276-277 and its gradient:
+ *   stats[0] = mean((returns - q_a)^2), stats[1] = mean(q_a);  dq [M, A] = (2 / M)(q_a - returns)
+ *   in the taken column, exact zeros elsewhere. One workgroup, a fixed summation order.
+ *   1 <= A <= 18; an action outside [0, A) is clamped into it (no out-of-range read).
+ *
+ * ocppo_clip_radam_step: ocppo_clip_adam_step's clip (same norm kernel, grad_scale, flat buffers,
+ * scalars and workspace: ocppo_clip_adam_workspace_bytes) followed by torch.optim.RAdam's step
+ * (no weight decay). rho_t and the rectification come from the device step count in double:
+ * with beta2 = 0.999 steps 1-5 are un-rectified (p -= lr * m / (1 - b1^t)), step 6 is the first
+ * rectified one. scalars[OCPPO_OPT_RECT] reports the rectification term (0: un-rectified).
+ * n_planes must be 0 (plane jobs are ocppo_clip_adam_step's).
+ * ------------------------------------------------------------------------------------------- */
+#define OCPPO_OPT_RECT 5
+OCPPO_API int ocppo_q_lambda(ocppo_stream_t stream, const float* rewards, const float* values,
+                             const float* dones, const float* next_q, const float* next_done,
+                             int64_t T, int64_t N, int64_t A, double gamma, double q_lambda,
+                             float* returns);
+OCPPO_API int ocppo_ln_relu_fwd(ocppo_stream_t stream, const float* x, const float* gamma,
+                                const float* beta, int64_t R, int64_t E, double eps, int relu,
+                                float* y, float* mean, float* rstd);
+OCPPO_API size_t ocppo_ln_relu_workspace_bytes(int64_t R, int64_t E);
+OCPPO_API int ocppo_ln_relu_bwd(ocppo_stream_t stream, const float* dy, const float* x,
+                                const float* y, const float* gamma, const float* mean,
+                                const float* rstd, int64_t R, int64_t E, int relu, float* dx,
+                                float* dgamma, float* dbeta, void* workspace,
+                                size_t workspace_bytes);
+OCPPO_API int ocppo_pqn_act(ocppo_stream_t stream, const float* hidden, int64_t N, int64_t H,
+                            const float* wq, const float* bq, int64_t A, uint64_t seed,
+                            const int64_t* step, int64_t step_offset, double start_e,
+                            double end_e, double duration, int64_t* actions, float* values,
+                            float* epsilon_out, float* q_out);
+OCPPO_API int ocppo_pqn_loss_fwd_bwd(ocppo_stream_t stream, const float* q, const int64_t* actions,
+                                     const float* returns, int64_t M, int64_t A, float* dq,
+                                     float* stats);
+OCPPO_API int ocppo_clip_radam_step(ocppo_stream_t stream, float* params, const float* grads,
+                                    float* exp_avg, float* exp_avg_sq, int64_t P, const float* lr,
+                                    double beta1, double beta2, double eps, double grad_scale,
+                                    double max_norm, float* scalars, void* workspace,
+                                    size_t workspace_bytes, int n_planes);
 
 #ifdef __cplusplus
 }

@@ -22,7 +22,7 @@ LIB_PATH = Path(os.environ.get("OCPPO_LIB", PKG / "lib" / "libocppo_hip.so"))
 HEADER = PKG.parent / "include" / "ocppo.h"
 
 # constants mirrored from include/ocppo.h (checked against the header by tests/test_abi.py)
-OCPPO_ABI_VERSION = 34
+OCPPO_ABI_VERSION = 35
 OCPPO_OK, OCPPO_E_INVALID, OCPPO_E_LAUNCH, OCPPO_E_WORKSPACE = 0, 1, 2, 3
 OCPPO_F32, OCPPO_BF16, OCPPO_U8 = 0, 1, 2
 OCPPO_X6_MBITS_ROWS = 2
@@ -156,6 +156,13 @@ SIGNATURES: dict[str, tuple[type, list]] = {
     "ocppo_lstm_seq_fwd": (I, [P, P, P, P, P, P, P, I64, I64, I64, P, P, P, P, P, P]),
     "ocppo_lstm_seq_bwd": (I, [P, P, P, P, P, P, P, I64, I64, I64, P]),
     "ocppo_lstm_step": (I, [P, P, P, P, P, P, P, I64, I64, I64, P, P]),
+    "ocppo_q_lambda": (I, [P, P, P, P, P, P, I64, I64, I64, D, D, P]),
+    "ocppo_ln_relu_fwd": (I, [P, P, P, P, I64, I64, D, I, P, P, P]),
+    "ocppo_ln_relu_workspace_bytes": (SZ, [I64, I64]),
+    "ocppo_ln_relu_bwd": (I, [P, P, P, P, P, P, P, I64, I64, I, P, P, P, P, SZ]),
+    "ocppo_pqn_act": (I, [P, P, I64, I64, P, P, I64, U64, P, I64, D, D, D, P, P, P, P]),
+    "ocppo_pqn_loss_fwd_bwd": (I, [P, P, P, P, I64, I64, P, P]),
+    "ocppo_clip_radam_step": (I, [P, P, P, P, P, I64, P, D, D, D, D, D, P, P, SZ, I]),
 }
 
 

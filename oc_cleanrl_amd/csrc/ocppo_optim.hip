@@ -273,3 +273,146 @@ extern "C" int ocppo_clip_adam_step(ocppo_stream_t stream, float* params, const 
                      static_cast<int>(nb), scalars, planes);
   return check_launch("ocppo_clip_adam_step/adam");
 }
+
+// ---- RAdam over the same flat buffers (torch.optim.RAdam, no weight decay) -----------------------
+// `optim.RAdam(q_network.parameters(), lr)` after `clip_grad_norm_(.., 10.0)` of
+// cleanrl/pqn_atari_envpool.py:194, 282-283. The norm pass is grad_norm_kernel above (it also
+// advances the step counter); radam_kernel combines its partials as adam_kernel does and derives,
+// from the device step count t, in double as torch's Python scalars are:
+//   bc1 = 1 - b1^t, bc2 = 1 - b2^t, rho_inf = 2 / (1 - b2) - 1, rho_t = rho_inf - 2 t b2^t / bc2
+//   rho_t > 5 : rect = sqrt((rho_t - 4)(rho_t - 2) rho_inf / ((rho_inf - 4)(rho_inf - 2) rho_t))
+//               p -= (m / bc1) * lr * (sqrt(bc2) / (sqrt(v) + eps)) * rect
+//   else      : p -= (m / bc1) * lr
+// with g = (g * grad_scale) * clip, m += (1 - b1) (g - m), v = b2 v + (1 - b2) g g per element.
+namespace ocppo {
+
+enum { S_RECT = 5 };
+
+struct RAdamScalars {
+  float clip, bc1, lr, adapt, rect, total, omb1, omb2;  // adapt = sqrt(bc2); rect = 0: the un-rectified step
+};
+
+__device__ __forceinline__ RAdamScalars radam_scalars(const float* __restrict__ partials, int nb,
+                                                      float max_norm,
+                                                      const float* __restrict__ lr, double b1,
+                                                      double b2,
+                                                      const float* __restrict__ scalars) {
+  __shared__ float red[kOptThreads / kWave];
+  __shared__ RAdamScalars sc;
+  float t = 0.f;
+  for (int b = threadIdx.x; b < nb; b += kOptThreads) t += partials[b];
+  const float tw = wave_sum(t);
+  const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
+  if (lane == 0) red[wid] = tw;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float s = red[0];
+    for (int k = 1; k < kOptThreads / kWave; ++k) s += red[k];
+    const float total = sqrtf(s);
+    float clip = 1.f;
+    if (max_norm > 0.f) {
+      clip = max_norm / (total + 1e-6f);
+      clip = clip < 1.f ? clip : 1.f;
+    }
+    const double step = static_cast<double>(scalars[S_STEP]);
+    const double b2t = pow(b2, step);
+    const double bc1 = 1.0 - pow(b1, step), bc2 = 1.0 - b2t;
+    const double rho_inf = 2.0 / (1.0 - b2) - 1.0;
+    const double rho_t = rho_inf - 2.0 * step * b2t / bc2;
+    double rect = 0.0;
+    if (rho_t > 5.0)
+      rect = sqrt((rho_t - 4.0) * (rho_t - 2.0) * rho_inf /
+                  ((rho_inf - 4.0) * (rho_inf - 2.0) * rho_t));
+    sc = RAdamScalars{clip, static_cast<float>(bc1), lr[0], static_cast<float>(sqrt(bc2)),
+                      static_cast<float>(rect), total, static_cast<float>(1.0 - b1),
+                      static_cast<float>(1.0 - b2)};
+  }
+  __syncthreads();
+  return sc;
+}
+
+__device__ __forceinline__ void radam_elem(float& p, float g, float& m, float& v, float b1,
+                                           float b2, const RAdamScalars& sc, float eps) {
+  // 1 - beta taken in double and rounded once, as torch's Python scalars are (1.f - 0.999f is
+  // 1.3e-5 off 0.001)
+  m = m + sc.omb1 * (g - m);
+  v = b2 * v + sc.omb2 * g * g;
+  float upd = (m / sc.bc1) * sc.lr;
+  if (sc.rect > 0.f) upd = upd * (sc.adapt / (sqrtf(v) + eps)) * sc.rect;
+  p = p - upd;
+}
+
+__global__ __launch_bounds__(kOptThreads) void radam_kernel(
+    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+    float* __restrict__ v, int64_t P, float grad_scale, float b1, float b2, float eps,
+    float max_norm, const float* __restrict__ lr, const float* __restrict__ partials, int nb,
+    float* __restrict__ scalars, double b1d, double b2d) {
+  // the betas as the doubles torch holds them: 1 - beta and the powers come from these
+  const RAdamScalars sc = radam_scalars(partials, nb, max_norm, lr, b1d, b2d, scalars);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {  // the reported figures (read after the step)
+    scalars[S_TOTAL_NORM] = sc.total;
+    scalars[S_CLIP] = sc.clip;
+    scalars[S_STEP_SIZE] = sc.lr / sc.bc1;
+    scalars[S_BC2_SQRT] = sc.adapt;
+    scalars[S_RECT] = sc.rect;
+  }
+  const float clip = sc.clip;
+  const int64_t P4 = P / 4;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * kOptThreads;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * kOptThreads + threadIdx.x; i < P4;
+       i += stride) {
+    float4 pp = reinterpret_cast<float4*>(p)[i];
+    const float4 gg = reinterpret_cast<const float4*>(g)[i];
+    float4 mm = reinterpret_cast<float4*>(m)[i];
+    float4 vv = reinterpret_cast<float4*>(v)[i];
+    radam_elem(pp.x, (gg.x * grad_scale) * clip, mm.x, vv.x, b1, b2, sc, eps);
+    radam_elem(pp.y, (gg.y * grad_scale) * clip, mm.y, vv.y, b1, b2, sc, eps);
+    radam_elem(pp.z, (gg.z * grad_scale) * clip, mm.z, vv.z, b1, b2, sc, eps);
+    radam_elem(pp.w, (gg.w * grad_scale) * clip, mm.w, vv.w, b1, b2, sc, eps);
+    reinterpret_cast<float4*>(p)[i] = pp;
+    reinterpret_cast<float4*>(m)[i] = mm;
+    reinterpret_cast<float4*>(v)[i] = vv;
+  }
+  if (blockIdx.x == 0)
+    for (int64_t i = 4 * P4 + threadIdx.x; i < P; i += kOptThreads)
+      radam_elem(p[i], (g[i] * grad_scale) * clip, m[i], v[i], b1, b2, sc, eps);
+}
+
+}  // namespace ocppo
+
+extern "C" int ocppo_clip_radam_step(ocppo_stream_t stream, float* params, const float* grads,
+                                     float* exp_avg, float* exp_avg_sq, int64_t P,
+                                     const float* lr, double beta1, double beta2, double eps,
+                                     double grad_scale, double max_norm, float* scalars,
+                                     void* workspace, size_t workspace_bytes, int n_planes) {
+  OCPPO_REQUIRE(P >= 0, "ocppo_clip_radam_step: bad size P=%lld", (long long)P);
+  OCPPO_REQUIRE(n_planes == 0, "ocppo_clip_radam_step: n_planes=%d: plane jobs are "
+                "ocppo_clip_adam_step's, this step writes none", n_planes);
+  OCPPO_REQUIRE(beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1,
+                "ocppo_clip_radam_step: betas (%g, %g) must be in [0, 1)", beta1, beta2);
+  if (P == 0) return OCPPO_OK;
+  OCPPO_REQUIRE(params && grads && exp_avg && exp_avg_sq && lr && scalars,
+                "ocppo_clip_radam_step: null pointer");
+  OCPPO_REQUIRE((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) |
+                 reinterpret_cast<uintptr_t>(exp_avg) | reinterpret_cast<uintptr_t>(exp_avg_sq)) %
+                        16 == 0,
+                "ocppo_clip_radam_step: buffers must be 16-byte aligned");
+  if (!workspace || workspace_bytes < ocppo_clip_adam_workspace_bytes(P))
+    return fail(OCPPO_E_WORKSPACE, "ocppo_clip_radam_step: workspace needs %zu bytes, got %zu",
+                ocppo_clip_adam_workspace_bytes(P), workspace_bytes);
+  float* partials = reinterpret_cast<float*>(static_cast<char*>(workspace) + 256);
+  int64_t nb = ceil_div(P / 4 > 0 ? P / 4 : 1, kOptThreads);
+  nb = nb < kOptBlocks ? nb : kOptBlocks;
+  clear_stale_error();
+  hipStream_t s = as_stream(stream);
+  hipLaunchKernelGGL(grad_norm_kernel, dim3(static_cast<unsigned>(nb)), dim3(kOptThreads), 0, s,
+                     grads, P, static_cast<float>(grad_scale), scalars, partials);
+  if (int rc = check_launch("ocppo_clip_radam_step/norm")) return rc;
+  int64_t na = nb < 256 * 8 ? nb : 256 * 8;
+  hipLaunchKernelGGL(radam_kernel, dim3(static_cast<unsigned>(na)), dim3(kOptThreads), 0, s, params,
+                     grads, exp_avg, exp_avg_sq, P, static_cast<float>(grad_scale),
+                     static_cast<float>(beta1), static_cast<float>(beta2),
+                     static_cast<float>(eps), static_cast<float>(max_norm), lr, partials,
+                     static_cast<int>(nb), scalars, beta1, beta2);
+  return check_launch("ocppo_clip_radam_step/radam");
+}

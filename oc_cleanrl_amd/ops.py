@@ -3126,3 +3126,177 @@ def lstm_step(x, w_ih, b_ih, w_hh, b_hh, done, h, c):
          _check(b_hh, "b_hh", f, dev, 4 * H), _check(done, "done", f, dev, N), N, I, H,
          _check(h, "h", f, dev, N * H), _check(c, "c", f, dev, N * H))
     return h, c
+
+
+# ---------------------------------------------------------------------------------------------
+# PQN (pqn_atari_envpool.py): Q(lambda), LayerNorm + ReLU, the Q head's acting step, the MSE loss
+# on the taken action and RAdam over the flat buffers (csrc/ocppo_pqn.hip, ocppo_optim.hip)
+# ---------------------------------------------------------------------------------------------
+LN_RELU_MAX_E = 1024
+PQN_MAX_ACTIONS, PQN_MAX_HIDDEN = 18, 1024
+
+
+def q_lambda(rewards, values, dones, next_q, next_done, gamma: float, q_lambda: float,
+             returns=None):
+    """The Q(lambda) targets of pqn_atari_envpool.py:248-261, bitwise the script's f32 loop:
+    rewards / values / dones [T, N] (values = the greedy Q stored at each step), next_q [N, A] =
+    q_network(next_obs), next_done [N] -> returns [T, N]."""
+    if rewards.dim() != 2 or next_q.dim() != 2:
+        raise ValueError(f"q_lambda: rewards must be [T, N] and next_q [N, A], got "
+                         f"{tuple(rewards.shape)}, {tuple(next_q.shape)}")
+    T, N = rewards.shape
+    A = next_q.shape[1]
+    dev, f = rewards.device, torch.float32
+    if returns is None:
+        returns = torch.empty_like(rewards)
+    call("ocppo_q_lambda", _stream(dev), _check(rewards, "rewards", f, dev),
+         _check(values, "values", f, dev, T * N), _check(dones, "dones", f, dev, T * N),
+         _check(next_q, "next_q", f, dev, N * A), _check(next_done, "next_done", f, dev, N), T, N,
+         A, float(gamma), float(q_lambda), _check(returns, "returns", f, dev, T * N))
+    return returns
+
+
+def _ln_relu_shape(x, weight, bias, who: str):
+    E = x.shape[-1] if x.dim() else 0
+    if x.dim() < 1 or weight.numel() != E or bias.numel() != E or not 1 <= E <= LN_RELU_MAX_E:
+        raise ValueError(f"{who}: x {tuple(x.shape)}, weight {tuple(weight.shape)}, bias "
+                         f"{tuple(bias.shape)} (one weight and bias per element of the last dim, "
+                         f"1 <= last dim <= {LN_RELU_MAX_E})")
+    return x.numel() // E, E
+
+
+def ln_relu_fwd(x, weight, bias, eps: float = 1e-5, relu: bool = True):
+    """relu(LayerNorm(x) * weight + bias) over the last dim (relu=False: plain LayerNorm) ->
+    (y, mean [R], rstd [R])."""
+    R, E = _ln_relu_shape(x, weight, bias, "ln_relu_fwd")
+    dev, f = x.device, torch.float32
+    px = _check(x, "x", f)
+    y = torch.empty_like(x)
+    mean = torch.empty(R, dtype=f, device=dev)
+    rstd = torch.empty(R, dtype=f, device=dev)
+    call("ocppo_ln_relu_fwd", _stream(dev), px, _check(weight, "weight", f, dev, E),
+         _check(bias, "bias", f, dev, E), R, E, float(eps), int(bool(relu)), y.data_ptr(),
+         mean.data_ptr(), rstd.data_ptr())
+    return y, mean, rstd
+
+
+def ln_relu_bwd(dy, x, y, weight, mean, rstd, relu: bool = True):
+    """(dx, dweight, dbias) of ln_relu_fwd; the ReLU mask is y > 0 (y is not read with
+    relu=False). Two launches: rows + per-workgroup partials, then their ordered sum."""
+    R, E = _ln_relu_shape(x, weight, weight, "ln_relu_bwd")
+    dev, f = x.device, torch.float32
+    px = _check(x, "x", f)
+    dx = torch.empty_like(x)
+    dw = torch.empty(E, dtype=f, device=dev)
+    db = torch.empty(E, dtype=f, device=dev)
+    nb = int(_lib.LIB.ocppo_ln_relu_workspace_bytes(R, E))
+    # one buffer per size: every call writes all the partials it reads, launches of a stream
+    # run one after another
+    ws = _persistent("ln_relu_bwd", dev, nb, lambda: torch.empty(
+        max(nb // 4, 1), dtype=f, device=dev))
+    call("ocppo_ln_relu_bwd", _stream(dev), _check(dy, "dy", f, dev, R * E), px,
+         _check(y, "y", f, dev, R * E) if relu else None, _check(weight, "weight", f, dev, E),
+         _check(mean, "mean", f, dev, R), _check(rstd, "rstd", f, dev, R), R, E,
+         int(bool(relu)), dx.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), nb)
+    return dx, dw, db
+
+
+class _LnRelu(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps: float, relu: bool):
+        x, w = x.detach().contiguous(), weight.detach()
+        y, mean, rstd = ln_relu_fwd(x, w, bias.detach(), eps, relu)
+        ctx.save_for_backward(x, y, w, mean, rstd)
+        ctx.relu = relu
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y, w, mean, rstd = ctx.saved_tensors
+        dx, dw, db = timed("ln_relu_bwd", lambda: ln_relu_bwd(g.contiguous(), x, y, w, mean, rstd,
+                                                              ctx.relu))
+        return dx, dw, db, None, None
+
+
+def ln_relu(x, weight, bias, eps: float = 1e-5, relu: bool = True):
+    """Differentiable relu(LayerNorm(x) * weight + bias) over the last dim: the LayerNorm -> ReLU
+    after every Linear of pqn_atari_envpool.py's QNetwork as one launch (two in the backward)."""
+    return _LnRelu.apply(x, weight, bias, eps, relu)
+
+
+def pqn_act_ok(hidden, wq) -> bool:
+    """pqn_act applies: GPU f32 [N, H] rows and an [A, H] head with A <= 18, H a multiple of 4 up
+    to 1024, both contiguous and 16-B aligned (q_head_epsilon_greedy's contract, widened)."""
+    if not (isinstance(hidden, torch.Tensor) and isinstance(wq, torch.Tensor) and hidden.is_cuda
+            and wq.is_cuda and hidden.dtype == wq.dtype == torch.float32 and hidden.dim() == 2
+            and wq.dim() == 2):
+        return False
+    H, A = hidden.shape[1], wq.shape[0]
+    return (wq.shape[1] == H and 1 <= A <= PQN_MAX_ACTIONS and 4 <= H <= PQN_MAX_HIDDEN
+            and H % 4 == 0 and hidden.is_contiguous() and wq.is_contiguous()
+            and (hidden.data_ptr() | wq.data_ptr()) % 16 == 0)
+
+
+def pqn_act(hidden, wq, bq, seed: int, step, start_e: float, end_e: float, duration: float,
+            actions_out=None, values_out=None, epsilon_out=None, step_offset: int = 0, q_out=None):
+    """The acting step of pqn_atari_envpool.py:224-232 in one launch: q = hidden @ wq.T + bq,
+    values = q's maximum (first index among equal maxima), actions = epsilon_greedy(q, ...)'s
+    for the same seed and step. Returns (actions, values)."""
+    if not pqn_act_ok(hidden, wq):
+        raise ValueError(f"pqn_act: hidden {tuple(getattr(hidden, 'shape', ()))}, wq "
+                         f"{tuple(getattr(wq, 'shape', ()))} outside pqn_act_ok")
+    N, H = hidden.shape
+    A = wq.shape[0]
+    dev, f = hidden.device, torch.float32
+    if actions_out is None:
+        actions_out = torch.empty(N, dtype=torch.int64, device=dev)
+    if values_out is None:
+        values_out = torch.empty(N, dtype=f, device=dev)
+    call("ocppo_pqn_act", _stream(dev), hidden.data_ptr(), N, H, wq.data_ptr(),
+         _check(bq, "bq", f, dev, A), A, int(seed) & 0xFFFFFFFFFFFFFFFF,
+         _check(step, "step", torch.int64, dev, 1), int(step_offset), float(start_e), float(end_e),
+         float(duration), _check(actions_out, "actions", torch.int64, dev, N),
+         _check(values_out, "values", f, dev, N), _opt(epsilon_out, "epsilon_out", f, dev, 1),
+         _opt(q_out, "q_out", f, dev, N * A))
+    return actions_out, values_out
+
+
+def pqn_loss_fwd_bwd(q, actions, returns, dq=None, stats=None):
+    """F.mse_loss(returns, q.gather(1, actions)) of pqn_atari_envpool.py:276-277 with its
+    gradient: (stats [2] = {td_loss, mean q(s, a)}, dq [M, A])."""
+    if q.dim() != 2 or not 1 <= q.shape[1] <= PQN_MAX_ACTIONS:
+        raise ValueError(f"pqn_loss_fwd_bwd: q must be [M, A <= {PQN_MAX_ACTIONS}], got "
+                         f"{tuple(q.shape)}")
+    M, A = q.shape
+    dev, f = q.device, torch.float32
+    pq = _check(q, "q", f)
+    if dq is None:
+        dq = torch.empty_like(q)
+    if stats is None:
+        stats = torch.empty(2, dtype=f, device=dev)
+    call("ocppo_pqn_loss_fwd_bwd", _stream(dev), pq,
+         _check(actions, "actions", torch.int64, dev, M), _check(returns, "returns", f, dev, M),
+         M, A, _check(dq, "dq", f, dev, M * A), _check(stats, "stats", f, dev, 2))
+    return stats, dq
+
+
+class FlatRAdam(FlatAdam):
+    """torch.optim.RAdam (betas (0.9, 0.999), eps 1e-8, no weight decay) + global-norm gradient
+    clipping over FlatAdam's flat buffers and views: the same clip and norm kernel, the step is
+    ocppo_clip_radam_step (rectification from the device step count; graph-capturable)."""
+
+    def __init__(self, params, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
+                 max_grad_norm: float = 0.0):
+        super().__init__(params, lr, betas, eps, max_grad_norm)
+
+    def write_planes(self, jobs):
+        if list(jobs):
+            raise ValueError("FlatRAdam writes no weight planes (ocppo_clip_radam_step takes no "
+                             "plane jobs)")
+
+    def step(self, grad_scale: float = 1.0):
+        dev = self.params.device
+        call("ocppo_clip_radam_step", _stream(dev), self.params.data_ptr(), self.grads.data_ptr(),
+             self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.numel,
+             self.lr.data_ptr(), self.betas[0], self.betas[1], self.eps, float(grad_scale),
+             self.max_grad_norm, self.scalars.data_ptr(), self.ws.data_ptr(), self.ws.numel(), 0)

@@ -365,8 +365,7 @@ class PPOTrainer:
             getattr(self.agent, "grads_in_place", True)
         if a.fused_optimizer:
             # every parameter becomes a view of one flat buffer; clip + Adam = 2 HIP launches
-            self.optimizer = ops.FlatAdam(self.agent.parameters(), lr=a.learning_rate, eps=1e-5,
-                                          max_grad_norm=a.max_grad_norm)
+            self.optimizer = self._make_optimizer()
             self.params = self.optimizer.param_list
             self.grad_buf = self.optimizer.grads
             self.lr = self.optimizer.lr
@@ -375,8 +374,7 @@ class PPOTrainer:
             self.params = grads.params
             self.grad_buf = grads.buf
             self.lr = torch.tensor(a.learning_rate, dtype=torch.float32, device=self.dev)
-            self.optimizer = torch.optim.Adam(self.params, lr=self.lr, eps=1e-5, fused=True,
-                                              capturable=True)
+            self.optimizer = self._make_torch_optimizer()
 
         T, N = self.T, self.N
         f32 = torch.float32
@@ -531,6 +529,17 @@ class PPOTrainer:
         a = self.args
         return make_agent(a.architecture, self.obs_shape, self.A, self.dev, a.encoder_dims,
                           a.decoder_dims)
+
+    def _make_optimizer(self):
+        """The fused optimizer over the agent's parameters (Args.fused_optimizer): an
+        ops.FlatAdam, or a subclass's own optimizer of the same interface."""
+        a = self.args
+        return ops.FlatAdam(self.agent.parameters(), lr=a.learning_rate, eps=1e-5,
+                            max_grad_norm=a.max_grad_norm)
+
+    def _make_torch_optimizer(self):
+        """torch's optimizer over self.params with the device lr self.lr (fused_optimizer off)."""
+        return torch.optim.Adam(self.params, lr=self.lr, eps=1e-5, fused=True, capturable=True)
 
     def _weight_planes(self):
         """ops.WeightPlanes of the PPObj Linear weights whose update forward / dX run on gemm_x6
