@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCPPO_ABI_VERSION 35
+#define OCPPO_ABI_VERSION 36
 
 /* status codes */
 #define OCPPO_OK 0
@@ -1364,6 +1364,69 @@ OCPPO_API int ocppo_clip_radam_step(ocppo_stream_t stream, float* params, const 
                                     double beta1, double beta2, double eps, double grad_scale,
                                     double max_norm, float* scalars, void* workspace,
                                     size_t workspace_bytes, int n_planes);
+
+/* ---------------------------------------------------------------------------------------------
+ * Discrete SAC (cleanrl/sac_atari.py) on the DQN loop, ABI 36. All f32, [B, A] row-major,
+ * 1 <= A <= 18. A negative B / E, an A outside the range or a null required pointer returns
+ * OCPPO_E_INVALID before any launch; B = 0 (E = 0) launches nothing and returns OCPPO_OK. One
+ * workgroup per loss launch, no atomics, a fixed summation order (the sums over the batch run in
+ * f64: a reported mean is the f32 nearest to the sum of its f32 terms). Graph-capturable; `alpha` is a
+ * device scalar, so no launch here needs a value from the host between train steps.
+ * probs are Categorical(logits=l).probs in torch.distributions' op order, log_pi is
+ * F.log_softmax(l) (:165-169).
+ *
+ * The critic launch (:283-302):
+ *   y_b  = rewards_b + ((1 - dones_b) * gamma) * sum_j p'_bj * (min(q1t_bj, q2t_bj) - alpha * logp'_bj)
+ *          with p', logp' from next_logits and q1t / q2t the two target critics on the next obs
+ *   stats = {qf1_loss, qf2_loss, mean_b q1[b, a_b], mean_b q2[b, a_b]},
+ *          qf_loss = mean_b (q[b, a_b] - y_b)^2
+ *   dq1, dq2 [B, A] = (2 / B)(q[b, a_b] - y_b) in the taken column, exact zeros elsewhere
+ *   y_out [B] may be NULL. An action outside [0, A) is clamped into it (no out-of-range read).
+ *
+ * The actor / temperature launch (:309-328), q1 / q2 the online critics AFTER the critic step:
+ *   g_bj = alpha * logp_bj - min(q1_bj, q2_bj);   actor_loss = mean_bj p_bj g_bj
+ *   dlogits_bk = p_bk (g_bk - sum_j p_bj g_bj) / (B A)
+ *   alpha_loss = mean_bj p_bj * (-exp(log_alpha) * (logp_bj + target_entropy))
+ *   autotune != 0: one torch.optim.Adam (single-tensor) step on *log_alpha with the gradient
+ *   exp(log_alpha) * (-mean_bj p_bj (logp_bj + target_entropy)), bias correction from
+ *   *adam_step + 1 (which is written back), then *alpha = exp(*log_alpha). autotune == 0: alpha,
+ *   log_alpha and the Adam state are not touched (the state pointers may be NULL), alpha_loss = 0.
+ *   stats = {actor_loss, alpha_loss, alpha after the launch, mean_b policy entropy}
+ *
+ * The acting launch (:248-252), t = *step + step_offset: t < learning_starts gives a uniform
+ * action in [0, A); otherwise one draw of Categorical(logits[e]) by the exponential race
+ * argmax_j p_j / e_j (first maximum), e_j ~ Exp(1) in double. Both from the library's counter
+ * stream (splitmix64 / unit53) under the SAC key, keyed by (seed, t, e, j). logits [E, A].
+ *
+ * ocppo_clip_adam_step_exact: ocppo_clip_adam_step (same norm pass, clip, flat buffers, scalars
+ * and workspace; no plane jobs) with torch.optim.Adam's scalars taken as torch takes them, from
+ * doubles: lr / (1 - beta1^t), sqrt(1 - beta2^t), 1 - beta1 and 1 - beta2 are formed in double and
+ * rounded to f32 once, and the element update is lerp_ / mul_().addcmul_() / addcdiv_() in torch's
+ * op order. ocppo_clip_adam_step forms them in f32, which a parameter that starts at zero shows
+ * whole (up to 6e-7 of the step from 1 - 0.9^t alone); its results are unchanged.
+ * ------------------------------------------------------------------------------------------- */
+OCPPO_API int ocppo_clip_adam_step_exact(ocppo_stream_t stream, float* params, const float* grads,
+                                         float* exp_avg, float* exp_avg_sq, int64_t P,
+                                         const float* lr, double beta1, double beta2, double eps,
+                                         double grad_scale, double max_norm, float* scalars,
+                                         void* workspace, size_t workspace_bytes);
+OCPPO_API int ocppo_sac_critic_loss_fwd_bwd(ocppo_stream_t stream, const float* next_logits,
+                                            const float* q1_next_target,
+                                            const float* q2_next_target, const float* q1,
+                                            const float* q2, const int64_t* actions,
+                                            const float* rewards, const float* dones, int64_t B,
+                                            int64_t A, double gamma, const float* alpha,
+                                            float* dq1, float* dq2, float* stats, float* y_out);
+OCPPO_API int ocppo_sac_actor_alpha_fwd_bwd(ocppo_stream_t stream, const float* logits,
+                                            const float* q1, const float* q2, int64_t B,
+                                            int64_t A, float* alpha, float* log_alpha,
+                                            double target_entropy, float* exp_avg,
+                                            float* exp_avg_sq, int64_t* adam_step, double lr,
+                                            double beta1, double beta2, double eps, int autotune,
+                                            float* dlogits, float* stats);
+OCPPO_API int ocppo_sac_act(ocppo_stream_t stream, const float* logits, int64_t E, int64_t A,
+                            uint64_t seed, const int64_t* step, int64_t step_offset,
+                            int64_t learning_starts, int64_t* actions);
 
 #ifdef __cplusplus
 }

@@ -22,7 +22,7 @@ LIB_PATH = Path(os.environ.get("OCPPO_LIB", PKG / "lib" / "libocppo_hip.so"))
 HEADER = PKG.parent / "include" / "ocppo.h"
 
 # constants mirrored from include/ocppo.h (checked against the header by tests/test_abi.py)
-OCPPO_ABI_VERSION = 35
+OCPPO_ABI_VERSION = 36
 OCPPO_OK, OCPPO_E_INVALID, OCPPO_E_LAUNCH, OCPPO_E_WORKSPACE = 0, 1, 2, 3
 OCPPO_F32, OCPPO_BF16, OCPPO_U8 = 0, 1, 2
 OCPPO_X6_MBITS_ROWS = 2
@@ -163,6 +163,11 @@ SIGNATURES: dict[str, tuple[type, list]] = {
     "ocppo_pqn_act": (I, [P, P, I64, I64, P, P, I64, U64, P, I64, D, D, D, P, P, P, P]),
     "ocppo_pqn_loss_fwd_bwd": (I, [P, P, P, P, I64, I64, P, P]),
     "ocppo_clip_radam_step": (I, [P, P, P, P, P, I64, P, D, D, D, D, D, P, P, SZ, I]),
+    "ocppo_sac_critic_loss_fwd_bwd": (I, [P, P, P, P, P, P, P, P, P, I64, I64, D, P, P, P, P, P]),
+    "ocppo_sac_actor_alpha_fwd_bwd": (I, [P, P, P, P, I64, I64, P, P, D, P, P, P, D, D, D, D, I,
+                                          P, P]),
+    "ocppo_sac_act": (I, [P, P, I64, I64, U64, P, I64, I64, P]),
+    "ocppo_clip_adam_step_exact": (I, [P, P, P, P, P, I64, P, D, D, D, D, D, P, P, SZ]),
 }
 
 

@@ -205,9 +205,80 @@ __global__ __launch_bounds__(kOptThreads) void adam_kernel(
       adam_elem(p[i], (g[i] * grad_scale) * clip, m[i], v[i], b1, b2, step_size, bc2_sqrt, eps);
 }
 
+// ---- Adam with torch's scalars -------------------------------------------------------------------
+// adam_kernel above forms 1 - beta^step, 1 - beta1 and 1 - beta2 in f32: one rounding of
+// 1 - 0.9^t is up to 6e-7 of the step size and 1 - 0.999f is 1.3e-5 off 0.001, which a parameter
+// that starts at zero (a bias) shows whole. torch.optim.Adam takes them from Python doubles:
+// step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t), the lerp weight 1 - beta1 and
+// addcmul's 1 - beta2, each rounded to f32 once. This kernel does that (the discrete SAC learner's
+// optimizers); the clip and the norm pass are adam_kernel's. No plane jobs.
+__global__ __launch_bounds__(kOptThreads) void adam_exact_kernel(
+    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+    float* __restrict__ v, int64_t P, float grad_scale, double b1, double b2, float eps,
+    float max_norm, const float* __restrict__ lr, const float* __restrict__ partials, int nb,
+    float* __restrict__ scalars) {
+  const AdamScalars sc0 = adam_scalars(partials, nb, max_norm, lr, static_cast<float>(b1),
+                                       static_cast<float>(b2), scalars);
+  const double step = static_cast<double>(scalars[S_STEP]);
+  const float step_size = static_cast<float>(static_cast<double>(lr[0]) / (1.0 - pow(b1, step)));
+  const float bc2_sqrt = static_cast<float>(sqrt(1.0 - pow(b2, step)));
+  const float omb1 = static_cast<float>(1.0 - b1), omb2 = static_cast<float>(1.0 - b2);
+  const float b2f = static_cast<float>(b2), clip = sc0.clip;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {  // the reported figures (S_STEP is not among them)
+    scalars[S_TOTAL_NORM] = sc0.total;
+    scalars[S_CLIP] = clip;
+    scalars[S_STEP_SIZE] = step_size;
+    scalars[S_BC2_SQRT] = bc2_sqrt;
+  }
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * kOptThreads + threadIdx.x; i < P;
+       i += static_cast<int64_t>(gridDim.x) * kOptThreads) {
+    const float gi = (g[i] * grad_scale) * clip;
+    float mi = m[i], vi = v[i];
+    mi = mi + omb1 * (gi - mi);            // exp_avg.lerp_(grad, 1 - beta1)
+    vi = vi * b2f + (omb2 * gi) * gi;      // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    p[i] = p[i] + ((-step_size) * mi) / denom;  // param.addcdiv_(exp_avg, denom, value=-step_size)
+    m[i] = mi;
+    v[i] = vi;
+  }
+}
+
 }  // namespace ocppo
 
 using namespace ocppo;
+
+extern "C" int ocppo_clip_adam_step_exact(ocppo_stream_t stream, float* params,
+                                          const float* grads, float* exp_avg, float* exp_avg_sq,
+                                          int64_t P, const float* lr, double beta1, double beta2,
+                                          double eps, double grad_scale, double max_norm,
+                                          float* scalars, void* workspace,
+                                          size_t workspace_bytes) {
+  OCPPO_REQUIRE(P > 0, "ocppo_clip_adam_step_exact: bad size P=%lld", (long long)P);
+  OCPPO_REQUIRE(params && grads && exp_avg && exp_avg_sq && lr && scalars,
+                "ocppo_clip_adam_step_exact: null pointer");
+  OCPPO_REQUIRE(beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1,
+                "ocppo_clip_adam_step_exact: betas must be in [0, 1)");
+  if (!workspace || workspace_bytes < 256 + kOptBlocks * sizeof(float))
+    return fail(OCPPO_E_WORKSPACE, "ocppo_clip_adam_step_exact: workspace needs %zu bytes, got %zu",
+                256 + kOptBlocks * sizeof(float), workspace_bytes);
+  float* partials = reinterpret_cast<float*>(static_cast<char*>(workspace) + 256);
+  int64_t nb = ceil_div(P / 4 > 0 ? P / 4 : 1, kOptThreads);
+  nb = nb < kOptBlocks ? nb : kOptBlocks;
+  OCPPO_REQUIRE(reinterpret_cast<uintptr_t>(grads) % 16 == 0,
+                "ocppo_clip_adam_step_exact: grads must be 16-byte aligned");
+  clear_stale_error();
+  hipStream_t s = as_stream(stream);
+  hipLaunchKernelGGL(grad_norm_kernel, dim3(static_cast<unsigned>(nb)), dim3(kOptThreads), 0, s,
+                     grads, P, static_cast<float>(grad_scale), scalars, partials);
+  if (int rc = check_launch("ocppo_clip_adam_step_exact/norm")) return rc;
+  int64_t na = ceil_div(P, kOptThreads);
+  na = na < 256 * 8 ? na : 256 * 8;
+  hipLaunchKernelGGL(adam_exact_kernel, dim3(static_cast<unsigned>(na)), dim3(kOptThreads), 0, s,
+                     params, grads, exp_avg, exp_avg_sq, P, static_cast<float>(grad_scale), beta1,
+                     beta2, static_cast<float>(eps), static_cast<float>(max_norm), lr, partials,
+                     static_cast<int>(nb), scalars);
+  return check_launch("ocppo_clip_adam_step_exact/adam");
+}
 
 extern "C" size_t ocppo_clip_adam_workspace_bytes(int64_t P) {
   (void)P;

@@ -185,7 +185,7 @@ class DQNTrainer:
         self.q = self._make_net().to(self.dev)
         self.target = self._make_net().to(self.dev)
         self.target.load_state_dict(self.q.state_dict())  # :315
-        self.opt = ops.FlatAdam(self.q.parameters(), lr=a.learning_rate, eps=self._adam_eps())
+        self.opt = self._make_optimizer(self.q.parameters(), a.learning_rate)
         # the target net's parameters as views of one flat buffer too (soft update = 2 ops)
         t_params = [p for p in self.target.parameters()]
         offs, n = ops.flat_offsets(t_params)
@@ -194,8 +194,7 @@ class DQNTrainer:
             self.t_flat[off:off + p.numel()].copy_(p.detach().reshape(-1))
             p.data = self.t_flat[off:off + p.numel()].view_as(p)
             p.requires_grad_(False)
-        self.direct_grads = all(isinstance(m, (nn.Linear, nn.ReLU, nn.Flatten))
-                                for m in self.q.network)
+        self.direct_grads = self._direct_grads()
 
         if a.obs_storage == "auto":
             st = torch.uint8 if self.pixels else torch.bfloat16
@@ -224,11 +223,7 @@ class DQNTrainer:
         self.dq = torch.zeros((B, self.A), dtype=f32, device=dev)
         self.td_stats = torch.zeros(2, dtype=f32, device=dev)
         self.duration = a.exploration_fraction * a.total_timesteps
-        # acting: the Q head and the epsilon-greedy choice in one launch
-        head = self.q.network[-1]
-        self.fused_act = (FUSED_ACT and isinstance(head, nn.Linear) and head.bias is not None and
-                          self.A <= 8 and head.in_features % 256 == 0 and
-                          head.in_features <= 1024)
+        self.fused_act = self._fused_act_ok()
         self.cur = 0  # index of the stack holding the current obs
         self.global_step = 0
         self.log_enabled = log
@@ -243,6 +238,19 @@ class DQNTrainer:
 
     def _adam_eps(self) -> float:
         return 1e-8  # optim.Adam's default
+
+    def _make_optimizer(self, params, lr: float):
+        return ops.FlatAdam(params, lr=lr, eps=self._adam_eps())
+
+    def _direct_grads(self) -> bool:
+        """Every layer of self.q writes its gradients in place (no zero_grad before backward)."""
+        return all(isinstance(m, (nn.Linear, nn.ReLU, nn.Flatten)) for m in self.q.network)
+
+    def _fused_act_ok(self) -> bool:
+        """Acting as the Q head and the epsilon-greedy choice in one launch."""
+        head = self.q.network[-1]
+        return (FUSED_ACT and isinstance(head, nn.Linear) and head.bias is not None and
+                self.A <= 8 and head.in_features % 256 == 0 and head.in_features <= 1024)
 
     def _make_replay(self, obs_dtype):
         # SB3 keeps buffer_size // n_envs rows of n_envs transitions (buffers.py:185)

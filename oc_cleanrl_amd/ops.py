@@ -3300,3 +3300,120 @@ class FlatRAdam(FlatAdam):
              self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.numel,
              self.lr.data_ptr(), self.betas[0], self.betas[1], self.eps, float(grad_scale),
              self.max_grad_norm, self.scalars.data_ptr(), self.ws.data_ptr(), self.ws.numel(), 0)
+
+
+# ---------------------------------------------------------------------------------------------
+# Discrete SAC (sac_atari.py): acting, twin soft-Q loss, policy + temperature loss and its Adam
+# ---------------------------------------------------------------------------------------------
+SAC_MAX_ACTIONS = C51_MAX_ACTIONS
+
+
+def _sac_shape(x, name: str):
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or not 1 <= x.shape[1] <= SAC_MAX_ACTIONS:
+        raise ValueError(f"{name} must be [rows, A <= {SAC_MAX_ACTIONS}], got "
+                         f"{tuple(getattr(x, 'shape', ()))}")
+    return x.shape
+
+
+def sac_act(logits, seed: int, step, learning_starts: int, actions_out=None,
+            step_offset: int = 0):
+    """sac_atari.py:248-252 in one launch: at t = step + step_offset < learning_starts a uniform
+    action per env, otherwise one draw of Categorical(logits) (the exponential race, first
+    maximum); the library's counter stream under the SAC key, keyed by (seed, t, env, j)."""
+    E, A = _sac_shape(logits, "sac_act: logits")
+    dev = logits.device
+    if actions_out is None:
+        actions_out = torch.empty(E, dtype=torch.int64, device=dev)
+    call("ocppo_sac_act", _stream(dev), _check(logits, "logits", torch.float32, dev), E, A,
+         int(seed) & 0xFFFFFFFFFFFFFFFF, _check(step, "step", torch.int64, dev, 1),
+         int(step_offset), int(learning_starts),
+         _check(actions_out, "actions", torch.int64, dev, E))
+    return actions_out
+
+
+def sac_critic_loss_fwd_bwd(next_logits, q1_next_target, q2_next_target, q1, q2, actions, rewards,
+                            dones, gamma: float, alpha, dq1=None, dq2=None, stats=None, y=None):
+    """sac_atari.py:283-302 in one launch: the soft target from the actor's logits and the two
+    target critics on the next observations, both MSE losses and d loss / d q1, d loss / d q2.
+    alpha: a device f32 scalar. Returns (stats [4] = {qf1_loss, qf2_loss, mean q1(s, a),
+    mean q2(s, a)}, dq1, dq2); y [B], if given, receives the targets."""
+    B, A = _sac_shape(q1, "sac_critic_loss_fwd_bwd: q1")
+    dev, f = q1.device, torch.float32
+    n = B * A
+    if dq1 is None:
+        dq1 = torch.empty_like(q1)
+    if dq2 is None:
+        dq2 = torch.empty_like(q1)
+    if stats is None:
+        stats = torch.empty(4, dtype=f, device=dev)
+    call("ocppo_sac_critic_loss_fwd_bwd", _stream(dev),
+         _check(next_logits, "next_logits", f, dev, n),
+         _check(q1_next_target, "q1_next_target", f, dev, n),
+         _check(q2_next_target, "q2_next_target", f, dev, n), _check(q1, "q1", f, dev, n),
+         _check(q2, "q2", f, dev, n), _check(actions, "actions", torch.int64, dev, B),
+         _check(rewards, "rewards", f, dev, B), _check(dones, "dones", f, dev, B), B, A,
+         float(gamma), _check(alpha, "alpha", f, dev, 1), _check(dq1, "dq1", f, dev, n),
+         _check(dq2, "dq2", f, dev, n), _check(stats, "stats", f, dev, 4),
+         _opt(y, "y", f, dev, B))
+    return stats, dq1, dq2
+
+
+class FlatAdamExact(FlatAdam):
+    """FlatAdam with torch.optim.Adam's step scalars formed as torch forms them, in double
+    (ocppo_clip_adam_step_exact): a bias that starts at zero then follows torch's to f32 rounding,
+    where FlatAdam's f32 `1 - beta^t` leaves up to 6e-7 of every step. FlatAdam itself (and what
+    the other learners compute) is unchanged. No weight planes."""
+
+    def write_planes(self, jobs):
+        if list(jobs):
+            raise ValueError("FlatAdamExact writes no weight planes")
+
+    def step(self, grad_scale: float = 1.0):
+        dev = self.params.device
+        call("ocppo_clip_adam_step_exact", _stream(dev), self.params.data_ptr(),
+             self.grads.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+             self.numel, self.lr.data_ptr(), self.betas[0], self.betas[1], self.eps,
+             float(grad_scale), self.max_grad_norm, self.scalars.data_ptr(), self.ws.data_ptr(),
+             self.ws.numel())
+
+
+class SacTemperature:
+    """The temperature of sac_atari.py:227-233 on the device: alpha, log_alpha and, with
+    autotune, log_alpha's Adam state (torch.optim.Adam([log_alpha], lr, eps=1e-4): exp_avg,
+    exp_avg_sq, step). sac_actor_alpha_fwd_bwd updates it in its launch."""
+
+    def __init__(self, device, autotune: bool, alpha: float, lr: float, target_entropy: float,
+                 betas=(0.9, 0.999), eps: float = 1e-4):
+        dev, f = torch.device(device), torch.float32
+        self.autotune = bool(autotune)
+        self.log_alpha = torch.zeros(1, dtype=f, device=dev)
+        # autotune: alpha = log_alpha.exp() = 1 (:229-230), else the flag's value
+        self.alpha = torch.full((1,), 1.0 if autotune else float(alpha), dtype=f, device=dev)
+        self.exp_avg = torch.zeros(1, dtype=f, device=dev)
+        self.exp_avg_sq = torch.zeros(1, dtype=f, device=dev)
+        self.step = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        self.target_entropy = float(target_entropy)
+
+
+def sac_actor_alpha_fwd_bwd(logits, q1, q2, temp: SacTemperature, dlogits=None, stats=None):
+    """sac_atari.py:309-328 in one launch: the policy loss and d loss / d logits, the temperature
+    loss and, with temp.autotune, log_alpha's Adam step and alpha = exp(log_alpha) (read by the
+    next critic launch). Returns (stats [4] = {actor_loss, alpha_loss, alpha, mean entropy},
+    dlogits)."""
+    B, A = _sac_shape(logits, "sac_actor_alpha_fwd_bwd: logits")
+    dev, f = logits.device, torch.float32
+    n = B * A
+    if dlogits is None:
+        dlogits = torch.empty_like(logits)
+    if stats is None:
+        stats = torch.empty(4, dtype=f, device=dev)
+    call("ocppo_sac_actor_alpha_fwd_bwd", _stream(dev), _check(logits, "logits", f, dev, n),
+         _check(q1, "q1", f, dev, n), _check(q2, "q2", f, dev, n), B, A,
+         _check(temp.alpha, "alpha", f, dev, 1), _check(temp.log_alpha, "log_alpha", f, dev, 1),
+         temp.target_entropy, _check(temp.exp_avg, "exp_avg", f, dev, 1),
+         _check(temp.exp_avg_sq, "exp_avg_sq", f, dev, 1),
+         _check(temp.step, "adam_step", torch.int64, dev, 1), temp.lr, temp.betas[0],
+         temp.betas[1], temp.eps, int(temp.autotune), _check(dlogits, "dlogits", f, dev, n),
+         _check(stats, "stats", f, dev, 4))
+    return stats, dlogits
