@@ -181,6 +181,10 @@ OCPPO_API int ocppo_ppo_loss_fwd_bwd(ocppo_stream_t stream, const float* logits,
  *   max_norm : <= 0 disables clipping
  * Math per element, f32: g = (g*grad_scale)*clip; m = b1*m + (1-b1)*g; v = b2*v + (1-b2)*g*g;
  * p -= (lr/(1-b1^t)) * m / (sqrt(v)/sqrt(1-b2^t) + eps)  (ATen's fused-Adam formula).
+ * ocppo_clip_adam_step, ocppo_clip_adam_step_exact and ocppo_clip_radam_step (below) are one norm
+ * launch and one step kernel: they share the argument checks (betas in [0, 1), all four buffers
+ * 16-byte aligned, the workspace), the clip, the scalars' layout and the vectorised body with its
+ * P % 4 tail, and differ in the step scalars and the per-element update alone.
  * ------------------------------------------------------------------------------------------- */
 #define OCPPO_OPT_STEP 0
 #define OCPPO_OPT_TOTAL_NORM 1
@@ -1335,7 +1339,8 @@ OCPPO_API int ocppo_lstm_step(ocppo_stream_t stream, const float* x, const float
  * (no weight decay). rho_t and the rectification come from the device step count in double:
  * with beta2 = 0.999 steps 1-5 are un-rectified (p -= lr * m / (1 - b1^t)), step 6 is the first
  * rectified one. scalars[OCPPO_OPT_RECT] reports the rectification term (0: un-rectified).
- * n_planes must be 0 (plane jobs are ocppo_clip_adam_step's).
+ * n_planes must be 0 (plane jobs are ocppo_clip_adam_step's). The launches, checks and kernel body
+ * are ocppo_clip_adam_step's; the rectification scalars and the element update are its own.
  * ------------------------------------------------------------------------------------------- */
 #define OCPPO_OPT_RECT 5
 OCPPO_API int ocppo_q_lambda(ocppo_stream_t stream, const float* rewards, const float* values,
@@ -1403,7 +1408,9 @@ OCPPO_API int ocppo_clip_radam_step(ocppo_stream_t stream, float* params, const 
  * doubles: lr / (1 - beta1^t), sqrt(1 - beta2^t), 1 - beta1 and 1 - beta2 are formed in double and
  * rounded to f32 once, and the element update is lerp_ / mul_().addcmul_() / addcdiv_() in torch's
  * op order. ocppo_clip_adam_step forms them in f32, which a parameter that starts at zero shows
- * whole (up to 6e-7 of the step from 1 - 0.9^t alone); its results are unchanged.
+ * whole (up to 6e-7 of the step from 1 - 0.9^t alone); its results are unchanged. It runs
+ * ocppo_clip_adam_step's vectorised kernel body, so params, grads, exp_avg and exp_avg_sq must all
+ * be 16-byte aligned (earlier only grads had to be).
  * ------------------------------------------------------------------------------------------- */
 OCPPO_API int ocppo_clip_adam_step_exact(ocppo_stream_t stream, float* params, const float* grads,
                                          float* exp_avg, float* exp_avg_sq, int64_t P,

@@ -29,15 +29,15 @@
 #include <math.h>
 
 #include "ocppo_common.h"
+#include "ocppo_layernorm.h"
 #include "ocppo_philox.h"
 
 namespace ocppo {
 
 constexpr int kAttnMaxS = 64;
+// residual add + LayerNorm: ocppo_layernorm.h's kernels at E <= 512, 8 columns per lane for every E
 constexpr int kLnMaxE = 512;
 constexpr int kLnPerLane = kLnMaxE / kWave;
-constexpr int kLnWaves = 4;
-constexpr int kLnMaxParts = 128;
 
 // sum_d a[d] * row[d]: four interleaved FMA chains, combined (0 + 1) + (2 + 3). Every score and
 // every dP of this file goes through here with the register operand first.
@@ -319,120 +319,6 @@ __global__ void philox_advance_kernel(int64_t* __restrict__ rng) {
   if (blockIdx.x == 0 && threadIdx.x == 0) rng[1] += 1;
 }
 
-// ---- residual add + LayerNorm -------------------------------------------------------------------
-// One wave per row; lane l holds columns l, l + 64, ... (E <= 512: at most 8 per lane).
-__global__ __launch_bounds__(kLnWaves* kWave) void add_layernorm_fwd_kernel(
-    const float* __restrict__ x, const float* __restrict__ res, const float* __restrict__ gamma,
-    const float* __restrict__ beta, int64_t R, int E, float eps, float* __restrict__ y,
-    float* __restrict__ mean, float* __restrict__ rstd) {
-  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
-  const float inv_e = 1.0f / static_cast<float>(E);
-  for (int64_t r = static_cast<int64_t>(blockIdx.x) * kLnWaves + wv; r < R;
-       r += static_cast<int64_t>(gridDim.x) * kLnWaves) {
-    float z[kLnPerLane];
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < kLnPerLane; ++k) {
-      const int e = lane + k * kWave;
-      z[k] = e < E ? x[r * E + e] + res[r * E + e] : 0.f;
-      s += z[k];
-    }
-    const float mu = wave_sum(s) * inv_e;
-    float sq = 0.f;
-#pragma unroll
-    for (int k = 0; k < kLnPerLane; ++k) {
-      const float d = lane + k * kWave < E ? z[k] - mu : 0.f;
-      sq += d * d;
-    }
-    const float rs = 1.0f / sqrtf(wave_sum(sq) * inv_e + eps);
-#pragma unroll
-    for (int k = 0; k < kLnPerLane; ++k) {
-      const int e = lane + k * kWave;
-      if (e < E) y[r * E + e] = (z[k] - mu) * rs * gamma[e] + beta[e];
-    }
-    if (lane == 0) {
-      mean[r] = mu;
-      rstd[r] = rs;
-    }
-  }
-}
-
-// dx per row, and this workgroup's dgamma / dbeta partial: rows blockIdx * 4 + wave, stepping by
-// the grid, summed per wave in row order, then waves 0..3 in order -> part[blockIdx][2][E]
-__global__ __launch_bounds__(kLnWaves* kWave) void add_layernorm_bwd_kernel(
-    const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ res,
-    const float* __restrict__ gamma, const float* __restrict__ mean,
-    const float* __restrict__ rstd, int64_t R, int E, float* __restrict__ dx,
-    float* __restrict__ part) {
-  __shared__ float s_g[kLnWaves][kLnMaxE], s_b[kLnWaves][kLnMaxE];
-  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
-  const float inv_e = 1.0f / static_cast<float>(E);
-  float gm[kLnPerLane], dg[kLnPerLane], db[kLnPerLane];
-#pragma unroll
-  for (int k = 0; k < kLnPerLane; ++k) {
-    const int e = lane + k * kWave;
-    gm[k] = e < E ? gamma[e] : 0.f;
-    dg[k] = db[k] = 0.f;
-  }
-  for (int64_t r = static_cast<int64_t>(blockIdx.x) * kLnWaves + wv; r < R;
-       r += static_cast<int64_t>(gridDim.x) * kLnWaves) {
-    const float mu = mean[r], rs = rstd[r];
-    float xh[kLnPerLane], g[kLnPerLane];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int k = 0; k < kLnPerLane; ++k) {
-      const int e = lane + k * kWave;
-      const bool in = e < E;
-      const float d = in ? dy[r * E + e] : 0.f;
-      xh[k] = in ? ((x[r * E + e] + res[r * E + e]) - mu) * rs : 0.f;
-      g[k] = d * gm[k];
-      s1 += g[k];
-      s2 += g[k] * xh[k];
-      dg[k] += d * xh[k];
-      db[k] += d;
-    }
-    const float c1 = wave_sum(s1) * inv_e, c2 = wave_sum(s2) * inv_e;
-#pragma unroll
-    for (int k = 0; k < kLnPerLane; ++k) {
-      const int e = lane + k * kWave;
-      if (e < E) dx[r * E + e] = rs * ((g[k] - c1) - xh[k] * c2);
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < kLnPerLane; ++k) {
-    s_g[wv][lane + k * kWave] = dg[k];
-    s_b[wv][lane + k * kWave] = db[k];
-  }
-  __syncthreads();
-  float* pg = part + static_cast<int64_t>(blockIdx.x) * 2 * E;
-  for (int e = threadIdx.x; e < E; e += kLnWaves * kWave) {
-    float a = s_g[0][e], c = s_b[0][e];
-    for (int w = 1; w < kLnWaves; ++w) {
-      a += s_g[w][e];
-      c += s_b[w][e];
-    }
-    pg[e] = a;
-    pg[E + e] = c;
-  }
-}
-
-// dgamma / dbeta = the partials summed in workgroup order
-__global__ __launch_bounds__(256) void add_layernorm_finish_kernel(
-    const float* __restrict__ part, int nb, int E, float* __restrict__ dgamma,
-    float* __restrict__ dbeta) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= 2 * E) return;
-  float a = 0.f;
-  for (int p = 0; p < nb; ++p) a += part[static_cast<int64_t>(p) * 2 * E + t];
-  if (t < E) dgamma[t] = a;
-  else dbeta[t - E] = a;
-}
-
-inline int ln_parts(int64_t R) {
-  const int64_t nb = ceil_div(R, kLnWaves);
-  return static_cast<int>(nb < kLnMaxParts ? (nb > 0 ? nb : 1) : kLnMaxParts);
-}
-
 inline int mha_check(const char* who, int64_t B, int64_t S, int64_t E, int64_t heads) {
   OCPPO_REQUIRE(B >= 1 && S >= 1 && S <= kAttnMaxS && E >= 1 && E <= 512 && heads >= 1 &&
                     E % heads == 0,
@@ -583,15 +469,15 @@ extern "C" int ocppo_add_layernorm_fwd(ocppo_stream_t stream, const float* x, co
   OCPPO_REQUIRE(x && res && gamma && beta && y && mean && rstd,
                 "ocppo_add_layernorm_fwd: null pointer");
   clear_stale_error();
-  hipLaunchKernelGGL(add_layernorm_fwd_kernel, dim3(grid_for(R, kLnWaves)),
-                     dim3(kLnWaves * kWave), 0, as_stream(stream), x, res, gamma, beta, R, (int)E,
-                     static_cast<float>(eps), y, mean, rstd);
+  hipLaunchKernelGGL((layernorm_fwd_kernel<LnAddResidual, kLnPerLane>),
+                     dim3(grid_for(R, kLnWaves)), dim3(kLnWaves * kWave), 0, as_stream(stream), x,
+                     res, gamma, beta, R, (int)E, static_cast<float>(eps), 0, y, mean, rstd);
   return check_launch("ocppo_add_layernorm_fwd");
 }
 
 extern "C" size_t ocppo_add_layernorm_workspace_bytes(int64_t R, int64_t E) {
   if (R < 0 || E < 1 || E > kLnMaxE) return 0;
-  return static_cast<size_t>(ln_parts(R)) * 2 * static_cast<size_t>(E) * sizeof(float);
+  return ln_workspace_bytes(R, E);
 }
 
 extern "C" int ocppo_add_layernorm_bwd(ocppo_stream_t stream, const float* dy, const float* x,
@@ -607,13 +493,8 @@ extern "C" int ocppo_add_layernorm_bwd(ocppo_stream_t stream, const float* dy, c
   if (!workspace || workspace_bytes < ocppo_add_layernorm_workspace_bytes(R, E))
     return fail(OCPPO_E_WORKSPACE, "ocppo_add_layernorm_bwd: workspace of %zu bytes, need %zu",
                 workspace_bytes, ocppo_add_layernorm_workspace_bytes(R, E));
-  const int nb = ln_parts(R);
-  float* part = static_cast<float*>(workspace);
   clear_stale_error();
-  hipLaunchKernelGGL(add_layernorm_bwd_kernel, dim3(nb), dim3(kLnWaves * kWave), 0,
-                     as_stream(stream), dy, x, res, gamma, mean, rstd, R, (int)E, dx, part);
-  if (int rc = check_launch("ocppo_add_layernorm_bwd")) return rc;
-  hipLaunchKernelGGL(add_layernorm_finish_kernel, dim3(static_cast<unsigned>(ceil_div(2 * E, 256))),
-                     dim3(256), 0, as_stream(stream), part, nb, (int)E, dgamma, dbeta);
-  return check_launch("ocppo_add_layernorm_bwd (finish)");
+  return ln_bwd_launch<LnAddResidual, kLnPerLane>(
+      "ocppo_add_layernorm_bwd", "ocppo_add_layernorm_bwd (finish)", as_stream(stream), dy, x, res,
+      nullptr, gamma, mean, rstd, R, E, 0, dx, dgamma, dbeta, static_cast<float*>(workspace));
 }

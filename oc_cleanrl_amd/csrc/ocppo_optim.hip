@@ -5,8 +5,8 @@
 //
 //   norm kernel : grid-strided partial sums of (g * grad_scale)^2 per workgroup (16-B loads),
 //                 one plain store per workgroup; workgroup 0 also advances the step counter
-//                 (the only writer of it; the adam kernel, next on the stream, only reads it)
-//   adam kernel : every workgroup first combines the <= 1024 partials itself, in a fixed order
+//                 (the only writer of it; the step kernel, next on the stream, only reads it)
+//   step kernel : every workgroup first combines the <= 1024 partials itself, in a fixed order
 //                 (the same fixed-order sum in every workgroup, so every one derives the same
 //                 total_norm, clip = min(max_norm / (total_norm + 1e-6), 1), step_size =
 //                 lr / (1 - beta1^step), bc2_sqrt = sqrt(1 - beta2^step)), then
@@ -16,6 +16,11 @@
 // No ticket and no last-arriver hand-off: the kernel boundary orders the partials (round 3's
 // ticketed form spent ~7 us of its 11 per minibatch in the 256-way fan-in and the dependent
 // combine at config 2).
+//
+// The same two launches serve ocppo_clip_adam_step_exact (torch.optim.Adam's scalars, from
+// doubles) and ocppo_clip_radam_step (torch.optim.RAdam): one norm kernel, one step kernel
+// (flat_step_kernel) instantiated with the rule that supplies the step scalars and the
+// per-element update, one host helper (flat_step) behind the three entries.
 #include "ocppo_common.h"
 #include "ocppo_x6split.h"
 
@@ -74,7 +79,7 @@ constexpr int kOptBlocks = 1024;  // grid-stride cap for the norm pass (4 workgr
                                   // most 1024 partials for every adam workgroup to combine
 
 // scalars layout (f32): see include/ocppo.h OCPPO_OPT_*
-enum { S_STEP = 0, S_TOTAL_NORM = 1, S_CLIP = 2, S_STEP_SIZE = 3, S_BC2_SQRT = 4 };
+enum { S_STEP = 0, S_TOTAL_NORM = 1, S_CLIP = 2, S_STEP_SIZE = 3, S_BC2_SQRT = 4, S_RECT = 5 };
 
 __global__ __launch_bounds__(kOptThreads) void grad_norm_kernel(
     const float* __restrict__ g, int64_t P, float grad_scale, float* __restrict__ scalars,
@@ -117,53 +122,152 @@ __global__ __launch_bounds__(kOptThreads) void grad_norm_kernel(
   }
 }
 
-// The step scalars from the norm kernel's partials, in every workgroup alike (fixed order: the
-// partial of workgroup t in thread t, the wave sums, then the 4 waves in order)
-struct AdamScalars {
-  float clip, step_size, bc2_sqrt, total;
+// The norm kernel's partials -> total_norm and the clip coefficient, in every workgroup alike
+// (fixed order: the partials t, t + 256, ... in thread t, the wave sums, then the 4 waves in order
+// by thread 0, the only thread whose return value is meaningful)
+struct NormClip {
+  float total, clip;
 };
-__device__ __forceinline__ AdamScalars adam_scalars(const float* __restrict__ partials, int nb,
-                                                    float max_norm, const float* __restrict__ lr,
-                                                    float beta1, float beta2,
-                                                    const float* __restrict__ scalars) {
+__device__ __forceinline__ NormClip norm_clip(const float* __restrict__ partials, int nb,
+                                              float max_norm) {
   __shared__ float red[kOptThreads / kWave];
-  __shared__ AdamScalars sc;
   float t = 0.f;
   for (int b = threadIdx.x; b < nb; b += kOptThreads) t += partials[b];
   const float tw = wave_sum(t);
   const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
   if (lane == 0) red[wid] = tw;
   __syncthreads();
+  NormClip nc{0.f, 1.f};
   if (threadIdx.x == 0) {
     float s = red[0];
     for (int k = 1; k < kOptThreads / kWave; ++k) s += red[k];
-    const float total = sqrtf(s);
-    float clip = 1.f;
+    nc.total = sqrtf(s);
     if (max_norm > 0.f) {
-      clip = max_norm / (total + 1e-6f);
-      clip = clip < 1.f ? clip : 1.f;
+      nc.clip = max_norm / (nc.total + 1e-6f);
+      nc.clip = nc.clip < 1.f ? nc.clip : 1.f;
     }
-    const float step = scalars[S_STEP];
-    sc = AdamScalars{clip, lr[0] / (1.f - powf(beta1, step)), sqrtf(1.f - powf(beta2, step)),
-                     total};
   }
-  __syncthreads();
-  return sc;
+  return nc;
 }
 
-__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float b1, float b2,
-                                          float step_size, float bc2_sqrt, float eps) {
-  m = b1 * m + (1.f - b1) * g;
-  v = b2 * v + (1.f - b2) * g * g;
-  const float denom = sqrtf(v) / bc2_sqrt + eps;
-  p = p - step_size * m / denom;
-}
+// ---- the three update rules -----------------------------------------------------------------------
+// A rule is what flat_step_kernel does not share: Scalars (what an element's update needs beside
+// the element; thread 0 of every workgroup builds them once from the clip, the device step count
+// t, lr and the betas), report (its figures in `scalars`) and elem (one element, g already scaled
+// and clipped). kPlanes: the step also serves AdamPlanes jobs; kMaxBlocks: the step's grid cap.
 
-__global__ __launch_bounds__(kOptThreads) void adam_kernel(
+// ATen's fused Adam with every scalar formed in f32 (the PPO learners' step; plane jobs)
+struct AdamRule {
+  static constexpr int kMaxBlocks = 256 * 8;
+  static constexpr bool kPlanes = true;
+  struct Scalars {
+    float clip, b1, b2, step_size, bc2_sqrt;
+  };
+  static __device__ Scalars scalars(NormClip nc, float step, float lr, double b1d, double b2d) {
+    const float b1 = static_cast<float>(b1d), b2 = static_cast<float>(b2d);
+    return Scalars{nc.clip, b1, b2, lr / (1.f - powf(b1, step)), sqrtf(1.f - powf(b2, step))};
+  }
+  static __device__ void report(const Scalars& sc, float* __restrict__ scalars) {
+    scalars[S_STEP_SIZE] = sc.step_size;
+    scalars[S_BC2_SQRT] = sc.bc2_sqrt;
+  }
+  static __device__ __forceinline__ void elem(float& p, float g, float& m, float& v,
+                                              const Scalars& sc, float eps) {
+    m = sc.b1 * m + (1.f - sc.b1) * g;
+    v = sc.b2 * v + (1.f - sc.b2) * g * g;
+    const float denom = sqrtf(v) / sc.bc2_sqrt + eps;
+    p = p - sc.step_size * m / denom;
+  }
+};
+
+// torch.optim.Adam with torch's scalars (the discrete SAC learner's optimizers). AdamRule forms
+// 1 - beta^t, 1 - beta1 and 1 - beta2 in f32: one rounding of 1 - 0.9^t is up to 6e-7 of the step
+// size and 1 - 0.999f is 1.3e-5 off 0.001, which a parameter that starts at zero (a bias) shows
+// whole. torch takes them from Python doubles: step_size = lr / (1 - beta1^t), bc2_sqrt =
+// sqrt(1 - beta2^t), the lerp weight 1 - beta1 and addcmul's 1 - beta2, each rounded to f32 once.
+struct AdamExactRule {
+  static constexpr int kMaxBlocks = 256 * 8;
+  static constexpr bool kPlanes = false;
+  struct Scalars {
+    float clip, omb1, omb2, b2, step_size, bc2_sqrt;
+  };
+  static __device__ Scalars scalars(NormClip nc, float stepf, float lr, double b1, double b2) {
+    const double step = static_cast<double>(stepf);
+    return Scalars{nc.clip,
+                   static_cast<float>(1.0 - b1),
+                   static_cast<float>(1.0 - b2),
+                   static_cast<float>(b2),
+                   static_cast<float>(static_cast<double>(lr) / (1.0 - pow(b1, step))),
+                   static_cast<float>(sqrt(1.0 - pow(b2, step)))};
+  }
+  static __device__ void report(const Scalars& sc, float* __restrict__ scalars) {
+    scalars[S_STEP_SIZE] = sc.step_size;
+    scalars[S_BC2_SQRT] = sc.bc2_sqrt;
+  }
+  static __device__ __forceinline__ void elem(float& p, float g, float& m, float& v,
+                                              const Scalars& sc, float eps) {
+    m = m + sc.omb1 * (g - m);          // exp_avg.lerp_(grad, 1 - beta1)
+    v = v * sc.b2 + (sc.omb2 * g) * g;  // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
+    const float denom = sqrtf(v) / sc.bc2_sqrt + eps;
+    p = p + ((-sc.step_size) * m) / denom;  // param.addcdiv_(exp_avg, denom, value=-step_size)
+  }
+};
+
+// torch.optim.RAdam, no weight decay: `optim.RAdam(q_network.parameters(), lr)` after
+// `clip_grad_norm_(.., 10.0)` of cleanrl/pqn_atari_envpool.py:194, 282-283. From the device step
+// count t, in double as torch's Python scalars are:
+//   bc1 = 1 - b1^t, bc2 = 1 - b2^t, rho_inf = 2 / (1 - b2) - 1, rho_t = rho_inf - 2 t b2^t / bc2
+//   rho_t > 5 : rect = sqrt((rho_t - 4)(rho_t - 2) rho_inf / ((rho_inf - 4)(rho_inf - 2) rho_t))
+//               p -= (m / bc1) * lr * (sqrt(bc2) / (sqrt(v) + eps)) * rect
+//   else      : p -= (m / bc1) * lr
+// with m += (1 - b1) (g - m), v = b2 v + (1 - b2) g g per element, 1 - beta taken in double and
+// rounded once (1.f - 0.999f is 1.3e-5 off 0.001).
+struct RAdamRule {
+  // every workgroup resident at once: the double-precision scalars are paid once, not per round
+  static constexpr int kMaxBlocks = kOptBlocks;
+  static constexpr bool kPlanes = false;
+  struct Scalars {
+    float clip, bc1, lr, adapt, rect, omb1, omb2, b2;  // adapt = sqrt(bc2); rect = 0: un-rectified
+  };
+  static __device__ Scalars scalars(NormClip nc, float stepf, float lr, double b1, double b2) {
+    const double step = static_cast<double>(stepf);
+    const double b2t = pow(b2, step);
+    const double bc1 = 1.0 - pow(b1, step), bc2 = 1.0 - b2t;
+    const double rho_inf = 2.0 / (1.0 - b2) - 1.0;
+    const double rho_t = rho_inf - 2.0 * step * b2t / bc2;
+    double rect = 0.0;
+    if (rho_t > 5.0)
+      rect = sqrt((rho_t - 4.0) * (rho_t - 2.0) * rho_inf /
+                  ((rho_inf - 4.0) * (rho_inf - 2.0) * rho_t));
+    return Scalars{nc.clip, static_cast<float>(bc1), lr, static_cast<float>(sqrt(bc2)),
+                   static_cast<float>(rect), static_cast<float>(1.0 - b1),
+                   static_cast<float>(1.0 - b2), static_cast<float>(b2)};
+  }
+  static __device__ void report(const Scalars& sc, float* __restrict__ scalars) {
+    scalars[S_STEP_SIZE] = sc.lr / sc.bc1;
+    scalars[S_BC2_SQRT] = sc.adapt;
+    scalars[S_RECT] = sc.rect;
+  }
+  static __device__ __forceinline__ void elem(float& p, float g, float& m, float& v,
+                                              const Scalars& sc, float eps) {
+    m = m + sc.omb1 * (g - m);
+    v = sc.b2 * v + sc.omb2 * g * g;
+    float upd = (m / sc.bc1) * sc.lr;
+    if (sc.rect > 0.f) upd = upd * (sc.adapt / (sqrtf(v) + eps)) * sc.rect;
+    p = p - upd;
+  }
+};
+
+// The step of every rule: 16-B vectors, 28 B of HBM per parameter, a grid-stride loop with the
+// next group's loads issued before this group's arithmetic is waited for, the P % 4 tail in
+// workgroup 0.
+template <class Rule>
+__global__ __launch_bounds__(kOptThreads) void flat_step_kernel(
     float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-    float* __restrict__ v, int64_t P, float grad_scale, float b1, float b2, float eps,
+    float* __restrict__ v, int64_t P, float grad_scale, double b1, double b2, float eps,
     float max_norm, const float* __restrict__ lr, const float* __restrict__ partials, int nb,
     float* __restrict__ scalars, AdamPlanes planes) {
+  __shared__ typename Rule::Scalars sc_lds;
   // the first element group's loads are issued before the scalars are combined: their latency
   // hides the partials' combine (at config 2 every thread has about one group)
   const int64_t P4 = P / 4;
@@ -176,23 +280,27 @@ __global__ __launch_bounds__(kOptThreads) void adam_kernel(
     mm = reinterpret_cast<float4*>(m)[i];
     vv = reinterpret_cast<float4*>(v)[i];
   }
-  const AdamScalars sc = adam_scalars(partials, nb, max_norm, lr, b1, b2, scalars);
-  if (blockIdx.x == 0 && threadIdx.x == 0) {  // the reported figures (read after the step)
-    scalars[S_TOTAL_NORM] = sc.total;
-    scalars[S_CLIP] = sc.clip;
-    scalars[S_STEP_SIZE] = sc.step_size;
-    scalars[S_BC2_SQRT] = sc.bc2_sqrt;
+  const NormClip nc = norm_clip(partials, nb, max_norm);
+  if (threadIdx.x == 0) {
+    sc_lds = Rule::scalars(nc, scalars[S_STEP], lr[0], b1, b2);
+    if (blockIdx.x == 0) {  // the reported figures (read after the step; S_STEP is the norm pass's)
+      scalars[S_TOTAL_NORM] = nc.total;
+      scalars[S_CLIP] = nc.clip;
+      Rule::report(sc_lds, scalars);
+    }
   }
-  const float clip = sc.clip, step_size = sc.step_size, bc2_sqrt = sc.bc2_sqrt;
+  __syncthreads();
+  const typename Rule::Scalars sc = sc_lds;
   for (; i < P4; i += stride) {
-    adam_elem(pp.x, (gg.x * grad_scale) * clip, mm.x, vv.x, b1, b2, step_size, bc2_sqrt, eps);
-    adam_elem(pp.y, (gg.y * grad_scale) * clip, mm.y, vv.y, b1, b2, step_size, bc2_sqrt, eps);
-    adam_elem(pp.z, (gg.z * grad_scale) * clip, mm.z, vv.z, b1, b2, step_size, bc2_sqrt, eps);
-    adam_elem(pp.w, (gg.w * grad_scale) * clip, mm.w, vv.w, b1, b2, step_size, bc2_sqrt, eps);
+    Rule::elem(pp.x, (gg.x * grad_scale) * sc.clip, mm.x, vv.x, sc, eps);
+    Rule::elem(pp.y, (gg.y * grad_scale) * sc.clip, mm.y, vv.y, sc, eps);
+    Rule::elem(pp.z, (gg.z * grad_scale) * sc.clip, mm.z, vv.z, sc, eps);
+    Rule::elem(pp.w, (gg.w * grad_scale) * sc.clip, mm.w, vv.w, sc, eps);
     reinterpret_cast<float4*>(p)[i] = pp;
     reinterpret_cast<float4*>(m)[i] = mm;
     reinterpret_cast<float4*>(v)[i] = vv;
-    if (planes.n) adam_planes_store(planes, i, pp);
+    if constexpr (Rule::kPlanes)
+      if (planes.n) adam_planes_store(planes, i, pp);
     if (i + stride < P4) {
       pp = reinterpret_cast<float4*>(p)[i + stride];
       gg = reinterpret_cast<const float4*>(g)[i + stride];
@@ -201,88 +309,55 @@ __global__ __launch_bounds__(kOptThreads) void adam_kernel(
     }
   }
   if (blockIdx.x == 0)
-    for (int64_t i = 4 * P4 + threadIdx.x; i < P; i += kOptThreads)
-      adam_elem(p[i], (g[i] * grad_scale) * clip, m[i], v[i], b1, b2, step_size, bc2_sqrt, eps);
+    for (int64_t j = 4 * P4 + threadIdx.x; j < P; j += kOptThreads)
+      Rule::elem(p[j], (g[j] * grad_scale) * sc.clip, m[j], v[j], sc, eps);
 }
 
-// ---- Adam with torch's scalars -------------------------------------------------------------------
-// adam_kernel above forms 1 - beta^step, 1 - beta1 and 1 - beta2 in f32: one rounding of
-// 1 - 0.9^t is up to 6e-7 of the step size and 1 - 0.999f is 1.3e-5 off 0.001, which a parameter
-// that starts at zero (a bias) shows whole. torch.optim.Adam takes them from Python doubles:
-// step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t), the lerp weight 1 - beta1 and
-// addcmul's 1 - beta2, each rounded to f32 once. This kernel does that (the discrete SAC learner's
-// optimizers); the clip and the norm pass are adam_kernel's. No plane jobs.
-__global__ __launch_bounds__(kOptThreads) void adam_exact_kernel(
-    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-    float* __restrict__ v, int64_t P, float grad_scale, double b1, double b2, float eps,
-    float max_norm, const float* __restrict__ lr, const float* __restrict__ partials, int nb,
-    float* __restrict__ scalars) {
-  const AdamScalars sc0 = adam_scalars(partials, nb, max_norm, lr, static_cast<float>(b1),
-                                       static_cast<float>(b2), scalars);
-  const double step = static_cast<double>(scalars[S_STEP]);
-  const float step_size = static_cast<float>(static_cast<double>(lr[0]) / (1.0 - pow(b1, step)));
-  const float bc2_sqrt = static_cast<float>(sqrt(1.0 - pow(b2, step)));
-  const float omb1 = static_cast<float>(1.0 - b1), omb2 = static_cast<float>(1.0 - b2);
-  const float b2f = static_cast<float>(b2), clip = sc0.clip;
-  if (blockIdx.x == 0 && threadIdx.x == 0) {  // the reported figures (S_STEP is not among them)
-    scalars[S_TOTAL_NORM] = sc0.total;
-    scalars[S_CLIP] = clip;
-    scalars[S_STEP_SIZE] = step_size;
-    scalars[S_BC2_SQRT] = bc2_sqrt;
-  }
-  for (int64_t i = static_cast<int64_t>(blockIdx.x) * kOptThreads + threadIdx.x; i < P;
-       i += static_cast<int64_t>(gridDim.x) * kOptThreads) {
-    const float gi = (g[i] * grad_scale) * clip;
-    float mi = m[i], vi = v[i];
-    mi = mi + omb1 * (gi - mi);            // exp_avg.lerp_(grad, 1 - beta1)
-    vi = vi * b2f + (omb2 * gi) * gi;      // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] = p[i] + ((-step_size) * mi) / denom;  // param.addcdiv_(exp_avg, denom, value=-step_size)
-    m[i] = mi;
-    v[i] = vi;
-  }
+constexpr size_t kOptWorkspaceBytes = 256 + kOptBlocks * sizeof(float);
+
+// What the three entries share once their own size and plane arguments are through: the checks,
+// the norm pass (which advances the step count) and the rule's step
+template <class Rule>
+static int flat_step(const char* who, ocppo_stream_t stream, float* params, const float* grads,
+                     float* exp_avg, float* exp_avg_sq, int64_t P, const float* lr, double beta1,
+                     double beta2, double eps, double grad_scale, double max_norm, float* scalars,
+                     void* workspace, size_t workspace_bytes, const AdamPlanes& planes) {
+  OCPPO_REQUIRE(params && grads && exp_avg && exp_avg_sq && lr && scalars, "%s: null pointer", who);
+  OCPPO_REQUIRE(beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1,
+                "%s: betas (%g, %g) must be in [0, 1)", who, beta1, beta2);
+  if (!workspace || workspace_bytes < kOptWorkspaceBytes)
+    return fail(OCPPO_E_WORKSPACE, "%s: workspace needs %zu bytes, got %zu", who,
+                kOptWorkspaceBytes, workspace_bytes);
+  OCPPO_REQUIRE((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) |
+                 reinterpret_cast<uintptr_t>(exp_avg) | reinterpret_cast<uintptr_t>(exp_avg_sq)) %
+                        16 == 0,
+                "%s: buffers must be 16-byte aligned", who);
+  float* partials = reinterpret_cast<float*>(static_cast<char*>(workspace) + 256);
+  const int64_t groups = ceil_div(P / 4 > 0 ? P / 4 : 1, kOptThreads);
+  const int64_t nb = groups < kOptBlocks ? groups : kOptBlocks;
+  const int64_t na = groups < Rule::kMaxBlocks ? groups : Rule::kMaxBlocks;
+  char what[96];
+  clear_stale_error();
+  hipStream_t s = as_stream(stream);
+  hipLaunchKernelGGL(grad_norm_kernel, dim3(static_cast<unsigned>(nb)), dim3(kOptThreads), 0, s,
+                     grads, P, static_cast<float>(grad_scale), scalars, partials);
+  snprintf(what, sizeof(what), "%s/norm", who);
+  if (int rc = check_launch(what)) return rc;
+  hipLaunchKernelGGL(flat_step_kernel<Rule>, dim3(static_cast<unsigned>(na)), dim3(kOptThreads), 0,
+                     s, params, grads, exp_avg, exp_avg_sq, P, static_cast<float>(grad_scale),
+                     beta1, beta2, static_cast<float>(eps), static_cast<float>(max_norm), lr,
+                     partials, static_cast<int>(nb), scalars, planes);
+  snprintf(what, sizeof(what), "%s/step", who);
+  return check_launch(what);
 }
 
 }  // namespace ocppo
 
 using namespace ocppo;
 
-extern "C" int ocppo_clip_adam_step_exact(ocppo_stream_t stream, float* params,
-                                          const float* grads, float* exp_avg, float* exp_avg_sq,
-                                          int64_t P, const float* lr, double beta1, double beta2,
-                                          double eps, double grad_scale, double max_norm,
-                                          float* scalars, void* workspace,
-                                          size_t workspace_bytes) {
-  OCPPO_REQUIRE(P > 0, "ocppo_clip_adam_step_exact: bad size P=%lld", (long long)P);
-  OCPPO_REQUIRE(params && grads && exp_avg && exp_avg_sq && lr && scalars,
-                "ocppo_clip_adam_step_exact: null pointer");
-  OCPPO_REQUIRE(beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1,
-                "ocppo_clip_adam_step_exact: betas must be in [0, 1)");
-  if (!workspace || workspace_bytes < 256 + kOptBlocks * sizeof(float))
-    return fail(OCPPO_E_WORKSPACE, "ocppo_clip_adam_step_exact: workspace needs %zu bytes, got %zu",
-                256 + kOptBlocks * sizeof(float), workspace_bytes);
-  float* partials = reinterpret_cast<float*>(static_cast<char*>(workspace) + 256);
-  int64_t nb = ceil_div(P / 4 > 0 ? P / 4 : 1, kOptThreads);
-  nb = nb < kOptBlocks ? nb : kOptBlocks;
-  OCPPO_REQUIRE(reinterpret_cast<uintptr_t>(grads) % 16 == 0,
-                "ocppo_clip_adam_step_exact: grads must be 16-byte aligned");
-  clear_stale_error();
-  hipStream_t s = as_stream(stream);
-  hipLaunchKernelGGL(grad_norm_kernel, dim3(static_cast<unsigned>(nb)), dim3(kOptThreads), 0, s,
-                     grads, P, static_cast<float>(grad_scale), scalars, partials);
-  if (int rc = check_launch("ocppo_clip_adam_step_exact/norm")) return rc;
-  int64_t na = ceil_div(P, kOptThreads);
-  na = na < 256 * 8 ? na : 256 * 8;
-  hipLaunchKernelGGL(adam_exact_kernel, dim3(static_cast<unsigned>(na)), dim3(kOptThreads), 0, s,
-                     params, grads, exp_avg, exp_avg_sq, P, static_cast<float>(grad_scale), beta1,
-                     beta2, static_cast<float>(eps), static_cast<float>(max_norm), lr, partials,
-                     static_cast<int>(nb), scalars);
-  return check_launch("ocppo_clip_adam_step_exact/adam");
-}
-
 extern "C" size_t ocppo_clip_adam_workspace_bytes(int64_t P) {
   (void)P;
-  return 256 + kOptBlocks * sizeof(float);
+  return kOptWorkspaceBytes;
 }
 
 extern "C" int ocppo_clip_adam_step(ocppo_stream_t stream, float* params, const float* grads,
@@ -317,139 +392,22 @@ extern "C" int ocppo_clip_adam_step(ocppo_stream_t stream, float* params, const 
     planes.trans[j] = plane_trans[j] ? 1 : 0;
     planes.dst[j] = static_cast<uint16_t*>(plane_dst[j]);
   }
-  OCPPO_REQUIRE(params && grads && exp_avg && exp_avg_sq && lr && scalars,
-                "ocppo_clip_adam_step: null pointer");
-  OCPPO_REQUIRE((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) |
-                 reinterpret_cast<uintptr_t>(exp_avg) | reinterpret_cast<uintptr_t>(exp_avg_sq)) %
-                        16 == 0,
-                "ocppo_clip_adam_step: buffers must be 16-byte aligned");
-  if (!workspace || workspace_bytes < ocppo_clip_adam_workspace_bytes(P))
-    return fail(OCPPO_E_WORKSPACE, "ocppo_clip_adam_step: workspace needs %zu bytes, got %zu",
-                ocppo_clip_adam_workspace_bytes(P), workspace_bytes);
-  char* ws = static_cast<char*>(workspace);
-  float* partials = reinterpret_cast<float*>(ws + 256);
-  int64_t nb = ceil_div(P / 4 > 0 ? P / 4 : 1, kOptThreads);
-  nb = nb < kOptBlocks ? nb : kOptBlocks;
-  clear_stale_error();
-  hipStream_t s = as_stream(stream);
-  hipLaunchKernelGGL(grad_norm_kernel, dim3(static_cast<unsigned>(nb)), dim3(kOptThreads), 0, s,
-                     grads, P, static_cast<float>(grad_scale), scalars, partials);
-  if (int rc = check_launch("ocppo_clip_adam_step/norm")) return rc;
-  int64_t na = ceil_div(P / 4 > 0 ? P / 4 : 1, kOptThreads);
-  na = na < 256 * 8 ? na : 256 * 8;
-  hipLaunchKernelGGL(adam_kernel, dim3(static_cast<unsigned>(na)), dim3(kOptThreads), 0, s, params,
-                     grads, exp_avg, exp_avg_sq, P, static_cast<float>(grad_scale),
-                     static_cast<float>(beta1), static_cast<float>(beta2),
-                     static_cast<float>(eps), static_cast<float>(max_norm), lr, partials,
-                     static_cast<int>(nb), scalars, planes);
-  return check_launch("ocppo_clip_adam_step/adam");
+  return flat_step<AdamRule>("ocppo_clip_adam_step", stream, params, grads, exp_avg, exp_avg_sq, P,
+                             lr, beta1, beta2, eps, grad_scale, max_norm, scalars, workspace,
+                             workspace_bytes, planes);
 }
 
-// ---- RAdam over the same flat buffers (torch.optim.RAdam, no weight decay) -----------------------
-// `optim.RAdam(q_network.parameters(), lr)` after `clip_grad_norm_(.., 10.0)` of
-// cleanrl/pqn_atari_envpool.py:194, 282-283. The norm pass is grad_norm_kernel above (it also
-// advances the step counter); radam_kernel combines its partials as adam_kernel does and derives,
-// from the device step count t, in double as torch's Python scalars are:
-//   bc1 = 1 - b1^t, bc2 = 1 - b2^t, rho_inf = 2 / (1 - b2) - 1, rho_t = rho_inf - 2 t b2^t / bc2
-//   rho_t > 5 : rect = sqrt((rho_t - 4)(rho_t - 2) rho_inf / ((rho_inf - 4)(rho_inf - 2) rho_t))
-//               p -= (m / bc1) * lr * (sqrt(bc2) / (sqrt(v) + eps)) * rect
-//   else      : p -= (m / bc1) * lr
-// with g = (g * grad_scale) * clip, m += (1 - b1) (g - m), v = b2 v + (1 - b2) g g per element.
-namespace ocppo {
-
-enum { S_RECT = 5 };
-
-struct RAdamScalars {
-  float clip, bc1, lr, adapt, rect, total, omb1, omb2;  // adapt = sqrt(bc2); rect = 0: the un-rectified step
-};
-
-__device__ __forceinline__ RAdamScalars radam_scalars(const float* __restrict__ partials, int nb,
-                                                      float max_norm,
-                                                      const float* __restrict__ lr, double b1,
-                                                      double b2,
-                                                      const float* __restrict__ scalars) {
-  __shared__ float red[kOptThreads / kWave];
-  __shared__ RAdamScalars sc;
-  float t = 0.f;
-  for (int b = threadIdx.x; b < nb; b += kOptThreads) t += partials[b];
-  const float tw = wave_sum(t);
-  const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
-  if (lane == 0) red[wid] = tw;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = red[0];
-    for (int k = 1; k < kOptThreads / kWave; ++k) s += red[k];
-    const float total = sqrtf(s);
-    float clip = 1.f;
-    if (max_norm > 0.f) {
-      clip = max_norm / (total + 1e-6f);
-      clip = clip < 1.f ? clip : 1.f;
-    }
-    const double step = static_cast<double>(scalars[S_STEP]);
-    const double b2t = pow(b2, step);
-    const double bc1 = 1.0 - pow(b1, step), bc2 = 1.0 - b2t;
-    const double rho_inf = 2.0 / (1.0 - b2) - 1.0;
-    const double rho_t = rho_inf - 2.0 * step * b2t / bc2;
-    double rect = 0.0;
-    if (rho_t > 5.0)
-      rect = sqrt((rho_t - 4.0) * (rho_t - 2.0) * rho_inf /
-                  ((rho_inf - 4.0) * (rho_inf - 2.0) * rho_t));
-    sc = RAdamScalars{clip, static_cast<float>(bc1), lr[0], static_cast<float>(sqrt(bc2)),
-                      static_cast<float>(rect), total, static_cast<float>(1.0 - b1),
-                      static_cast<float>(1.0 - b2)};
-  }
-  __syncthreads();
-  return sc;
+extern "C" int ocppo_clip_adam_step_exact(ocppo_stream_t stream, float* params,
+                                          const float* grads, float* exp_avg, float* exp_avg_sq,
+                                          int64_t P, const float* lr, double beta1, double beta2,
+                                          double eps, double grad_scale, double max_norm,
+                                          float* scalars, void* workspace,
+                                          size_t workspace_bytes) {
+  OCPPO_REQUIRE(P > 0, "ocppo_clip_adam_step_exact: bad size P=%lld", (long long)P);
+  return flat_step<AdamExactRule>("ocppo_clip_adam_step_exact", stream, params, grads, exp_avg,
+                                  exp_avg_sq, P, lr, beta1, beta2, eps, grad_scale, max_norm,
+                                  scalars, workspace, workspace_bytes, AdamPlanes{});
 }
-
-__device__ __forceinline__ void radam_elem(float& p, float g, float& m, float& v, float b1,
-                                           float b2, const RAdamScalars& sc, float eps) {
-  // 1 - beta taken in double and rounded once, as torch's Python scalars are (1.f - 0.999f is
-  // 1.3e-5 off 0.001)
-  m = m + sc.omb1 * (g - m);
-  v = b2 * v + sc.omb2 * g * g;
-  float upd = (m / sc.bc1) * sc.lr;
-  if (sc.rect > 0.f) upd = upd * (sc.adapt / (sqrtf(v) + eps)) * sc.rect;
-  p = p - upd;
-}
-
-__global__ __launch_bounds__(kOptThreads) void radam_kernel(
-    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-    float* __restrict__ v, int64_t P, float grad_scale, float b1, float b2, float eps,
-    float max_norm, const float* __restrict__ lr, const float* __restrict__ partials, int nb,
-    float* __restrict__ scalars, double b1d, double b2d) {
-  // the betas as the doubles torch holds them: 1 - beta and the powers come from these
-  const RAdamScalars sc = radam_scalars(partials, nb, max_norm, lr, b1d, b2d, scalars);
-  if (blockIdx.x == 0 && threadIdx.x == 0) {  // the reported figures (read after the step)
-    scalars[S_TOTAL_NORM] = sc.total;
-    scalars[S_CLIP] = sc.clip;
-    scalars[S_STEP_SIZE] = sc.lr / sc.bc1;
-    scalars[S_BC2_SQRT] = sc.adapt;
-    scalars[S_RECT] = sc.rect;
-  }
-  const float clip = sc.clip;
-  const int64_t P4 = P / 4;
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * kOptThreads;
-  for (int64_t i = static_cast<int64_t>(blockIdx.x) * kOptThreads + threadIdx.x; i < P4;
-       i += stride) {
-    float4 pp = reinterpret_cast<float4*>(p)[i];
-    const float4 gg = reinterpret_cast<const float4*>(g)[i];
-    float4 mm = reinterpret_cast<float4*>(m)[i];
-    float4 vv = reinterpret_cast<float4*>(v)[i];
-    radam_elem(pp.x, (gg.x * grad_scale) * clip, mm.x, vv.x, b1, b2, sc, eps);
-    radam_elem(pp.y, (gg.y * grad_scale) * clip, mm.y, vv.y, b1, b2, sc, eps);
-    radam_elem(pp.z, (gg.z * grad_scale) * clip, mm.z, vv.z, b1, b2, sc, eps);
-    radam_elem(pp.w, (gg.w * grad_scale) * clip, mm.w, vv.w, b1, b2, sc, eps);
-    reinterpret_cast<float4*>(p)[i] = pp;
-    reinterpret_cast<float4*>(m)[i] = mm;
-    reinterpret_cast<float4*>(v)[i] = vv;
-  }
-  if (blockIdx.x == 0)
-    for (int64_t i = 4 * P4 + threadIdx.x; i < P; i += kOptThreads)
-      radam_elem(p[i], (g[i] * grad_scale) * clip, m[i], v[i], b1, b2, sc, eps);
-}
-
-}  // namespace ocppo
 
 extern "C" int ocppo_clip_radam_step(ocppo_stream_t stream, float* params, const float* grads,
                                      float* exp_avg, float* exp_avg_sq, int64_t P,
@@ -459,31 +417,9 @@ extern "C" int ocppo_clip_radam_step(ocppo_stream_t stream, float* params, const
   OCPPO_REQUIRE(P >= 0, "ocppo_clip_radam_step: bad size P=%lld", (long long)P);
   OCPPO_REQUIRE(n_planes == 0, "ocppo_clip_radam_step: n_planes=%d: plane jobs are "
                 "ocppo_clip_adam_step's, this step writes none", n_planes);
-  OCPPO_REQUIRE(beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1,
-                "ocppo_clip_radam_step: betas (%g, %g) must be in [0, 1)", beta1, beta2);
   if (P == 0) return OCPPO_OK;
-  OCPPO_REQUIRE(params && grads && exp_avg && exp_avg_sq && lr && scalars,
-                "ocppo_clip_radam_step: null pointer");
-  OCPPO_REQUIRE((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) |
-                 reinterpret_cast<uintptr_t>(exp_avg) | reinterpret_cast<uintptr_t>(exp_avg_sq)) %
-                        16 == 0,
-                "ocppo_clip_radam_step: buffers must be 16-byte aligned");
-  if (!workspace || workspace_bytes < ocppo_clip_adam_workspace_bytes(P))
-    return fail(OCPPO_E_WORKSPACE, "ocppo_clip_radam_step: workspace needs %zu bytes, got %zu",
-                ocppo_clip_adam_workspace_bytes(P), workspace_bytes);
-  float* partials = reinterpret_cast<float*>(static_cast<char*>(workspace) + 256);
-  int64_t nb = ceil_div(P / 4 > 0 ? P / 4 : 1, kOptThreads);
-  nb = nb < kOptBlocks ? nb : kOptBlocks;
-  clear_stale_error();
-  hipStream_t s = as_stream(stream);
-  hipLaunchKernelGGL(grad_norm_kernel, dim3(static_cast<unsigned>(nb)), dim3(kOptThreads), 0, s,
-                     grads, P, static_cast<float>(grad_scale), scalars, partials);
-  if (int rc = check_launch("ocppo_clip_radam_step/norm")) return rc;
-  int64_t na = nb < 256 * 8 ? nb : 256 * 8;
-  hipLaunchKernelGGL(radam_kernel, dim3(static_cast<unsigned>(na)), dim3(kOptThreads), 0, s, params,
-                     grads, exp_avg, exp_avg_sq, P, static_cast<float>(grad_scale),
-                     static_cast<float>(beta1), static_cast<float>(beta2),
-                     static_cast<float>(eps), static_cast<float>(max_norm), lr, partials,
-                     static_cast<int>(nb), scalars, beta1, beta2);
-  return check_launch("ocppo_clip_radam_step/radam");
+  return flat_step<RAdamRule>("ocppo_clip_radam_step", stream, params, grads, exp_avg, exp_avg_sq,
+                              P, lr, beta1, beta2, eps, grad_scale, max_norm, scalars, workspace,
+                              workspace_bytes, AdamPlanes{});
 }
+

@@ -4,9 +4,13 @@
 // the rollout rows (:224-232), and the MSE loss on the taken action's Q value (:276-277). All f32,
 // wave64, no atomics: every sum runs in an order fixed by the shapes alone.
 #include "ocppo_common.h"
+#include "ocppo_layernorm.h"
 #include "ocppo_rng.h"
 
 namespace ocppo {
+
+// LayerNorm + ReLU: ocppo_layernorm.h's kernels with the two-step centring, E <= 1024
+constexpr int kLnrMaxE = 1024;
 
 // ---- Q(lambda) -----------------------------------------------------------------------------------
 // One thread per environment walks t = T-1 .. 0 (consecutive lanes = consecutive envs of a time
@@ -35,156 +39,6 @@ __global__ __launch_bounds__(256) void q_lambda_kernel(
     last = rew[gi] + (g * mix) * nnt;
     ret[gi] = last;
   }
-}
-
-// ---- LayerNorm + ReLU ----------------------------------------------------------------------------
-// One wave per row; lane l holds columns l, l + 64, ... (PL per lane, E <= 64 PL). The row is
-// centred in two steps so that a large common offset costs nothing: d = z - mu0 with mu0 a first
-// estimate of the mean (the plain sum / E in the forward, the saved mean in the backward), then
-// c = sum(d) / E and d -= c. d is then the deviation from the mean to f32 precision of the
-// DEVIATIONS, and the variance is sum(d^2) / E about it (never E[x^2] - mean^2).
-constexpr int kLnrWaves = 4;
-constexpr int kLnrMaxE = 1024;
-constexpr int kLnrMaxParts = 128;
-
-template <int PL>
-__device__ __forceinline__ float lnr_center(float (&d)[PL], int lane, int E, float mu0,
-                                            float inv_e) {
-  float s = 0.f;
-#pragma unroll
-  for (int k = 0; k < PL; ++k) {
-    d[k] = lane + k * kWave < E ? d[k] - mu0 : 0.f;
-    s += d[k];
-  }
-  const float c = wave_sum(s) * inv_e;
-#pragma unroll
-  for (int k = 0; k < PL; ++k) d[k] = lane + k * kWave < E ? d[k] - c : 0.f;
-  return c;
-}
-
-template <int PL>
-__global__ __launch_bounds__(kLnrWaves* kWave) void ln_relu_fwd_kernel(
-    const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
-    int64_t R, int E, float eps, int relu, float* __restrict__ y, float* __restrict__ mean,
-    float* __restrict__ rstd) {
-  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
-  const float inv_e = 1.0f / static_cast<float>(E);
-  for (int64_t r = static_cast<int64_t>(blockIdx.x) * kLnrWaves + wv; r < R;
-       r += static_cast<int64_t>(gridDim.x) * kLnrWaves) {
-    float d[PL];
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < PL; ++k) {
-      const int e = lane + k * kWave;
-      d[k] = e < E ? x[r * E + e] : 0.f;
-      s += d[k];
-    }
-    const float mu0 = wave_sum(s) * inv_e;
-    const float c = lnr_center<PL>(d, lane, E, mu0, inv_e);
-    float sq = 0.f;
-#pragma unroll
-    for (int k = 0; k < PL; ++k) sq += d[k] * d[k];
-    const float rs = 1.0f / sqrtf(wave_sum(sq) * inv_e + eps);
-#pragma unroll
-    for (int k = 0; k < PL; ++k) {
-      const int e = lane + k * kWave;
-      if (e < E) {
-        const float v = (d[k] * rs) * gamma[e] + beta[e];
-        y[r * E + e] = relu ? relu_f(v) : v;
-      }
-    }
-    if (lane == 0) {
-      mean[r] = mu0 + c;
-      rstd[r] = rs;
-    }
-  }
-}
-
-// dx per row, and this workgroup's dgamma / dbeta partial: rows blockIdx * 4 + wave, stepping by
-// the grid, summed per wave in row order, then waves 0..3 in order -> part[blockIdx][2][E].
-// relu: dy is masked with y > 0 first.
-template <int PL>
-__global__ __launch_bounds__(kLnrWaves* kWave) void ln_relu_bwd_kernel(
-    const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ y,
-    const float* __restrict__ gamma, const float* __restrict__ mean,
-    const float* __restrict__ rstd, int64_t R, int E, int relu, float* __restrict__ dx,
-    float* __restrict__ part) {
-  __shared__ float s_g[kLnrWaves][PL * kWave], s_b[kLnrWaves][PL * kWave];
-  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
-  const float inv_e = 1.0f / static_cast<float>(E);
-  float gm[PL], dg[PL], db[PL];
-#pragma unroll
-  for (int k = 0; k < PL; ++k) {
-    const int e = lane + k * kWave;
-    gm[k] = e < E ? gamma[e] : 0.f;
-    dg[k] = db[k] = 0.f;
-  }
-  for (int64_t r = static_cast<int64_t>(blockIdx.x) * kLnrWaves + wv; r < R;
-       r += static_cast<int64_t>(gridDim.x) * kLnrWaves) {
-    const float rs = rstd[r];
-    float xh[PL], g[PL];
-#pragma unroll
-    for (int k = 0; k < PL; ++k) {
-      const int e = lane + k * kWave;
-      xh[k] = e < E ? x[r * E + e] : 0.f;
-    }
-    lnr_center<PL>(xh, lane, E, mean[r], inv_e);
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int k = 0; k < PL; ++k) {
-      const int e = lane + k * kWave;
-      float d = 0.f;
-      if (e < E) {
-        d = dy[r * E + e];
-        if (relu && !(y[r * E + e] > 0.f)) d = 0.f;
-      }
-      xh[k] = xh[k] * rs;
-      g[k] = d * gm[k];
-      s1 += g[k];
-      s2 += g[k] * xh[k];
-      dg[k] += d * xh[k];
-      db[k] += d;
-    }
-    const float c1 = wave_sum(s1) * inv_e, c2 = wave_sum(s2) * inv_e;
-#pragma unroll
-    for (int k = 0; k < PL; ++k) {
-      const int e = lane + k * kWave;
-      if (e < E) dx[r * E + e] = rs * ((g[k] - c1) - xh[k] * c2);
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < PL; ++k) {
-    s_g[wv][lane + k * kWave] = dg[k];
-    s_b[wv][lane + k * kWave] = db[k];
-  }
-  __syncthreads();
-  float* pg = part + static_cast<int64_t>(blockIdx.x) * 2 * E;
-  for (int e = threadIdx.x; e < E; e += kLnrWaves * kWave) {
-    float a = s_g[0][e], c = s_b[0][e];
-    for (int w = 1; w < kLnrWaves; ++w) {
-      a += s_g[w][e];
-      c += s_b[w][e];
-    }
-    pg[e] = a;
-    pg[E + e] = c;
-  }
-}
-
-// dgamma / dbeta = the partials summed in workgroup order
-__global__ __launch_bounds__(256) void ln_relu_finish_kernel(const float* __restrict__ part, int nb,
-                                                             int E, float* __restrict__ dgamma,
-                                                             float* __restrict__ dbeta) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= 2 * E) return;
-  float a = 0.f;
-  for (int p = 0; p < nb; ++p) a += part[static_cast<int64_t>(p) * 2 * E + t];
-  if (t < E) dgamma[t] = a;
-  else dbeta[t - E] = a;
-}
-
-inline int lnr_parts(int64_t R) {
-  const int64_t nb = ceil_div(R, kLnrWaves);
-  return static_cast<int>(nb < kLnrMaxParts ? (nb > 0 ? nb : 1) : kLnrMaxParts);
 }
 
 // ---- Q head + greedy value + epsilon-greedy action ----------------------------------------------
@@ -303,6 +157,12 @@ static int lnr_check(const char* who, int64_t R, int64_t E) {
   return OCPPO_OK;
 }
 
+// columns per lane: 2, 8 or 16 at E <= 128, <= 512 and above
+#define OCPPO_LNR_DISPATCH(E, CALL)                   \
+  if ((E) <= 128) { constexpr int PL = 2; CALL; }     \
+  else if ((E) <= 512) { constexpr int PL = 8; CALL; } \
+  else { constexpr int PL = 16; CALL; }
+
 extern "C" int ocppo_ln_relu_fwd(ocppo_stream_t stream, const float* x, const float* gamma,
                                  const float* beta, int64_t R, int64_t E, double eps, int relu,
                                  float* y, float* mean, float* rstd) {
@@ -310,21 +170,16 @@ extern "C" int ocppo_ln_relu_fwd(ocppo_stream_t stream, const float* x, const fl
   if (R == 0) return OCPPO_OK;
   OCPPO_REQUIRE(x && gamma && beta && y && mean && rstd, "ocppo_ln_relu_fwd: null pointer");
   clear_stale_error();
-  const dim3 grid(grid_for(R, kLnrWaves)), block(kLnrWaves * kWave);
-  hipStream_t s = as_stream(stream);
-#define OCPPO_LNF(PL)                                                                      \
-  hipLaunchKernelGGL(ln_relu_fwd_kernel<PL>, grid, block, 0, s, x, gamma, beta, R, (int)E, \
-                     static_cast<float>(eps), relu ? 1 : 0, y, mean, rstd)
-  if (E <= 128) OCPPO_LNF(2);
-  else if (E <= 512) OCPPO_LNF(8);
-  else OCPPO_LNF(16);
-#undef OCPPO_LNF
+  OCPPO_LNR_DISPATCH(E, hipLaunchKernelGGL((layernorm_fwd_kernel<LnRelu, PL>),
+                                           dim3(grid_for(R, kLnWaves)), dim3(kLnWaves * kWave), 0,
+                                           as_stream(stream), x, nullptr, gamma, beta, R, (int)E,
+                                           static_cast<float>(eps), relu ? 1 : 0, y, mean, rstd));
   return check_launch("ocppo_ln_relu_fwd");
 }
 
 extern "C" size_t ocppo_ln_relu_workspace_bytes(int64_t R, int64_t E) {
   if (R < 0 || E < 1 || E > kLnrMaxE) return 0;
-  return static_cast<size_t>(lnr_parts(R)) * 2 * static_cast<size_t>(E) * sizeof(float);
+  return ln_workspace_bytes(R, E);
 }
 
 extern "C" int ocppo_ln_relu_bwd(ocppo_stream_t stream, const float* dy, const float* x,
@@ -339,23 +194,13 @@ extern "C" int ocppo_ln_relu_bwd(ocppo_stream_t stream, const float* dy, const f
   if (!workspace || workspace_bytes < ocppo_ln_relu_workspace_bytes(R, E))
     return fail(OCPPO_E_WORKSPACE, "ocppo_ln_relu_bwd: workspace of %zu bytes, need %zu",
                 workspace_bytes, ocppo_ln_relu_workspace_bytes(R, E));
-  const int nb = lnr_parts(R);
-  float* part = static_cast<float*>(workspace);
   clear_stale_error();
-  const dim3 grid(nb), block(kLnrWaves * kWave);
-  hipStream_t s = as_stream(stream);
-#define OCPPO_LNB(PL)                                                                          \
-  hipLaunchKernelGGL(ln_relu_bwd_kernel<PL>, grid, block, 0, s, dy, x, y, gamma, mean, rstd, R, \
-                     (int)E, relu ? 1 : 0, dx, part)
-  if (E <= 128) OCPPO_LNB(2);
-  else if (E <= 512) OCPPO_LNB(8);
-  else OCPPO_LNB(16);
-#undef OCPPO_LNB
-  if (int rc = check_launch("ocppo_ln_relu_bwd")) return rc;
-  hipLaunchKernelGGL(ln_relu_finish_kernel, dim3(static_cast<unsigned>(ceil_div(2 * E, 256))),
-                     dim3(256), 0, s, part, nb, (int)E, dgamma, dbeta);
-  return check_launch("ocppo_ln_relu_bwd (finish)");
+  OCPPO_LNR_DISPATCH(E, return (ln_bwd_launch<LnRelu, PL>(
+                            "ocppo_ln_relu_bwd", "ocppo_ln_relu_bwd (finish)", as_stream(stream),
+                            dy, x, nullptr, y, gamma, mean, rstd, R, E, relu ? 1 : 0, dx, dgamma,
+                            dbeta, static_cast<float*>(workspace))));
 }
+#undef OCPPO_LNR_DISPATCH
 
 extern "C" int ocppo_pqn_act(ocppo_stream_t stream, const float* hidden, int64_t N, int64_t H,
                              const float* wq, const float* bq, int64_t A, uint64_t seed,

@@ -2242,7 +2242,14 @@ class FlatAdam:
     """Adam (torch.optim.Adam semantics, eps as given) + global-norm gradient clipping over ONE
     flat f32 parameter buffer. Construct it over the module's parameters: every parameter becomes
     a view of `self.params` and its `.grad` a view of `self.grads` (so the DP all-reduce is one
-    call). `step()` is two HIP launches and is graph-capturable (step count, lr on device)."""
+    call). `step()` is two HIP launches and is graph-capturable (step count, lr on device).
+
+    A subclass is another update rule over the same buffers and the same step(): it names its
+    entry, and with NO_PLANES (why it takes no plane jobs, the entry's arguments in their place)
+    write_planes refuses."""
+
+    ENTRY = "ocppo_clip_adam_step"
+    NO_PLANES = None
 
     def __init__(self, params, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
                  max_grad_norm: float = 0.0):
@@ -2273,7 +2280,9 @@ class FlatAdam:
         self.max_grad_norm = float(max_grad_norm)
         nb = _lib.LIB.ocppo_clip_adam_workspace_bytes(n)
         self.ws = torch.zeros(int(nb), dtype=torch.uint8, device=dev)
-        self._planes = (0, None, None, None, None, None)
+        # the entry's arguments after the workspace
+        self._planes = ((0, None, None, None, None, None) if self.NO_PLANES is None
+                        else self.NO_PLANES[1])
 
     def write_planes(self, jobs):
         """jobs [(weight, trans, planes)] (WeightPlanes.jobs): every step also writes each
@@ -2281,6 +2290,10 @@ class FlatAdam:
         trans) into planes, so the next GEMMs need no split launch (ocppo_clip_adam_step's plane
         jobs, <= 8)."""
         jobs = list(jobs)
+        if self.NO_PLANES is not None:
+            if jobs:
+                raise ValueError(self.NO_PLANES[0])
+            return
         if len(jobs) > 8:
             raise ValueError("FlatAdam.write_planes: at most 8 weights")
         base = self.params.data_ptr()
@@ -2309,7 +2322,7 @@ class FlatAdam:
 
     def step(self, grad_scale: float = 1.0):
         dev = self.params.device
-        call("ocppo_clip_adam_step", _stream(dev), self.params.data_ptr(), self.grads.data_ptr(),
+        call(self.ENTRY, _stream(dev), self.params.data_ptr(), self.grads.data_ptr(),
              self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.numel,
              self.lr.data_ptr(), self.betas[0], self.betas[1], self.eps, float(grad_scale),
              self.max_grad_norm, self.scalars.data_ptr(), self.ws.data_ptr(), self.ws.numel(),
@@ -2935,42 +2948,66 @@ def mha(qkv, key_valid, heads: int, rng=None, site: int = 0, p: float = 0.0):
     return _MHADropout.apply(qkv, key_valid, heads, rng, site, float(p))
 
 
-def _ln_shape(x, res, weight, who: str):
-    E = x.shape[-1]
-    if x.shape != res.shape or weight.numel() != E or not 1 <= E <= MHA_MAX_E:
-        raise ValueError(f"{who}: x {tuple(x.shape)}, res {tuple(res.shape)}, weight "
-                         f"{tuple(weight.shape)} (same shapes, last dim <= {MHA_MAX_E})")
+# The two LayerNorms (add_layernorm_* here, ln_relu_* with the PQN kernels below) are one kernel
+# skeleton (csrc/ocppo_layernorm.h) behind two pairs of entries; so are their wrappers.
+def _ln_shape(x, res, weight, bias, max_e: int, who: str):
+    """(rows, E) of a LayerNorm over x's last dim."""
+    E = x.shape[-1] if x.dim() else 0
+    if (not 1 <= E <= max_e or weight.numel() != E or (bias is not None and bias.numel() != E)
+            or (res is not None and res.shape != x.shape)):
+        shapes = [f"{n} {tuple(t.shape)}" for n, t in (("x", x), ("res", res), ("weight", weight),
+                                                       ("bias", bias)) if t is not None]
+        raise ValueError(f"{who}: {', '.join(shapes)} (one weight and bias per element of the "
+                         f"last dim, 1 <= last dim <= {max_e}, res shaped as x)")
     return x.numel() // E, E
 
 
-def add_layernorm_fwd(x, res, weight, bias, eps: float):
-    """LayerNorm(x + res) * weight + bias over the last dim -> (y, mean [R], rstd [R])."""
-    R, E = _ln_shape(x, res, weight, "add_layernorm_fwd")
+def _ln_fwd(entry: str, x, res, weight, bias, eps: float, max_e: int, flags=()):
+    """`entry`'s launch -> (y, mean [R], rstd [R]); res (or None) and flags as the entry takes
+    them."""
+    R, E = _ln_shape(x, res, weight, bias, max_e, entry)
     dev, f = x.device, torch.float32
+    rows = [_check(t, n, f, dev) for n, t in (("x", x), ("res", res)) if t is not None]
     y = torch.empty_like(x)
     mean = torch.empty(R, dtype=f, device=dev)
     rstd = torch.empty(R, dtype=f, device=dev)
-    call("ocppo_add_layernorm_fwd", _stream(dev), _check(x, "x", f, dev), _check(res, "res", f, dev),
-         _check(weight, "weight", f, dev, E), _check(bias, "bias", f, dev, E), R, E, float(eps),
-         y.data_ptr(), mean.data_ptr(), rstd.data_ptr())
+    call(entry, _stream(dev), *rows, _check(weight, "weight", f, dev, E),
+         _check(bias, "bias", f, dev, E), R, E, float(eps), *flags, y.data_ptr(), mean.data_ptr(),
+         rstd.data_ptr())
     return y, mean, rstd
 
 
-def add_layernorm_bwd(dy, x, res, weight, mean, rstd):
-    """(dx, dweight, dbias) of add_layernorm_fwd; x + res is recomputed from the two inputs, dx
-    is the gradient of both. Two launches: rows + per-workgroup partials, then their ordered sum."""
-    R, E = _ln_shape(x, res, weight, "add_layernorm_bwd")
+def _ln_bwd(entry: str, workspace, dy, x, weight, mean, rstd, max_e: int, res=None, y=None,
+            flags=()):
+    """`entry`'s two launches (rows + per-workgroup partials, then their ordered sum) ->
+    (dx, dweight, dbias). res or y: the entry's third row input (y may be None); workspace(bytes,
+    device): the partials' buffer, fully written before it is read."""
+    R, E = _ln_shape(x, res, weight, None, max_e, entry)
     dev, f = x.device, torch.float32
     dx = torch.empty_like(x)
     dw = torch.empty(E, dtype=f, device=dev)
     db = torch.empty(E, dtype=f, device=dev)
-    nb = int(_lib.LIB.ocppo_add_layernorm_workspace_bytes(R, E))
-    ws = torch.empty(nb // 4, dtype=f, device=dev)  # fully written before it is read
-    call("ocppo_add_layernorm_bwd", _stream(dev), _check(dy, "dy", f, dev, R * E),
-         _check(x, "x", f, dev), _check(res, "res", f, dev), _check(weight, "weight", f, dev, E),
-         _check(mean, "mean", f, dev, R), _check(rstd, "rstd", f, dev, R), R, E, dx.data_ptr(),
-         dw.data_ptr(), db.data_ptr(), ws.data_ptr(), nb)
+    nb = int(getattr(_lib.LIB, entry.replace("_bwd", "_workspace_bytes"))(R, E))
+    ws = workspace(nb, dev)
+    third = ("res", res) if res is not None else ("y", y)
+    call(entry, _stream(dev), _check(dy, "dy", f, dev, R * E), _check(x, "x", f, dev),
+         _opt(third[1], third[0], f, dev, R * E), _check(weight, "weight", f, dev, E),
+         _check(mean, "mean", f, dev, R), _check(rstd, "rstd", f, dev, R), R, E, *flags,
+         dx.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), nb)
     return dx, dw, db
+
+
+def add_layernorm_fwd(x, res, weight, bias, eps: float):
+    """LayerNorm(x + res) * weight + bias over the last dim -> (y, mean [R], rstd [R])."""
+    return _ln_fwd("ocppo_add_layernorm_fwd", x, res, weight, bias, eps, MHA_MAX_E)
+
+
+def add_layernorm_bwd(dy, x, res, weight, mean, rstd):
+    """(dx, dweight, dbias) of add_layernorm_fwd; x + res is recomputed from the two inputs, dx
+    is the gradient of both."""
+    return _ln_bwd("ocppo_add_layernorm_bwd",
+                   lambda nb, dev: torch.empty(nb // 4, dtype=torch.float32, device=dev),
+                   dy, x, weight, mean, rstd, MHA_MAX_E, res=res)
 
 
 class _AddLayerNorm(torch.autograd.Function):
@@ -3156,49 +3193,22 @@ def q_lambda(rewards, values, dones, next_q, next_done, gamma: float, q_lambda: 
     return returns
 
 
-def _ln_relu_shape(x, weight, bias, who: str):
-    E = x.shape[-1] if x.dim() else 0
-    if x.dim() < 1 or weight.numel() != E or bias.numel() != E or not 1 <= E <= LN_RELU_MAX_E:
-        raise ValueError(f"{who}: x {tuple(x.shape)}, weight {tuple(weight.shape)}, bias "
-                         f"{tuple(bias.shape)} (one weight and bias per element of the last dim, "
-                         f"1 <= last dim <= {LN_RELU_MAX_E})")
-    return x.numel() // E, E
-
-
 def ln_relu_fwd(x, weight, bias, eps: float = 1e-5, relu: bool = True):
     """relu(LayerNorm(x) * weight + bias) over the last dim (relu=False: plain LayerNorm) ->
     (y, mean [R], rstd [R])."""
-    R, E = _ln_relu_shape(x, weight, bias, "ln_relu_fwd")
-    dev, f = x.device, torch.float32
-    px = _check(x, "x", f)
-    y = torch.empty_like(x)
-    mean = torch.empty(R, dtype=f, device=dev)
-    rstd = torch.empty(R, dtype=f, device=dev)
-    call("ocppo_ln_relu_fwd", _stream(dev), px, _check(weight, "weight", f, dev, E),
-         _check(bias, "bias", f, dev, E), R, E, float(eps), int(bool(relu)), y.data_ptr(),
-         mean.data_ptr(), rstd.data_ptr())
-    return y, mean, rstd
+    return _ln_fwd("ocppo_ln_relu_fwd", x, None, weight, bias, eps, LN_RELU_MAX_E,
+                   (int(bool(relu)),))
 
 
 def ln_relu_bwd(dy, x, y, weight, mean, rstd, relu: bool = True):
     """(dx, dweight, dbias) of ln_relu_fwd; the ReLU mask is y > 0 (y is not read with
-    relu=False). Two launches: rows + per-workgroup partials, then their ordered sum."""
-    R, E = _ln_relu_shape(x, weight, weight, "ln_relu_bwd")
-    dev, f = x.device, torch.float32
-    px = _check(x, "x", f)
-    dx = torch.empty_like(x)
-    dw = torch.empty(E, dtype=f, device=dev)
-    db = torch.empty(E, dtype=f, device=dev)
-    nb = int(_lib.LIB.ocppo_ln_relu_workspace_bytes(R, E))
-    # one buffer per size: every call writes all the partials it reads, launches of a stream
-    # run one after another
-    ws = _persistent("ln_relu_bwd", dev, nb, lambda: torch.empty(
-        max(nb // 4, 1), dtype=f, device=dev))
-    call("ocppo_ln_relu_bwd", _stream(dev), _check(dy, "dy", f, dev, R * E), px,
-         _check(y, "y", f, dev, R * E) if relu else None, _check(weight, "weight", f, dev, E),
-         _check(mean, "mean", f, dev, R), _check(rstd, "rstd", f, dev, R), R, E,
-         int(bool(relu)), dx.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), nb)
-    return dx, dw, db
+    relu=False). The partials live in one buffer per size: every call writes all the partials it
+    reads, launches of a stream run one after another."""
+    return _ln_bwd("ocppo_ln_relu_bwd",
+                   lambda nb, dev: _persistent("ln_relu_bwd", dev, nb, lambda: torch.empty(
+                       max(nb // 4, 1), dtype=torch.float32, device=dev)),
+                   dy, x, weight, mean, rstd, LN_RELU_MAX_E, y=y if relu else None,
+                   flags=(int(bool(relu)),))
 
 
 class _LnRelu(torch.autograd.Function):
@@ -3285,21 +3295,9 @@ class FlatRAdam(FlatAdam):
     clipping over FlatAdam's flat buffers and views: the same clip and norm kernel, the step is
     ocppo_clip_radam_step (rectification from the device step count; graph-capturable)."""
 
-    def __init__(self, params, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
-                 max_grad_norm: float = 0.0):
-        super().__init__(params, lr, betas, eps, max_grad_norm)
-
-    def write_planes(self, jobs):
-        if list(jobs):
-            raise ValueError("FlatRAdam writes no weight planes (ocppo_clip_radam_step takes no "
-                             "plane jobs)")
-
-    def step(self, grad_scale: float = 1.0):
-        dev = self.params.device
-        call("ocppo_clip_radam_step", _stream(dev), self.params.data_ptr(), self.grads.data_ptr(),
-             self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.numel,
-             self.lr.data_ptr(), self.betas[0], self.betas[1], self.eps, float(grad_scale),
-             self.max_grad_norm, self.scalars.data_ptr(), self.ws.data_ptr(), self.ws.numel(), 0)
+    ENTRY = "ocppo_clip_radam_step"
+    NO_PLANES = ("FlatRAdam writes no weight planes (ocppo_clip_radam_step takes no plane jobs)",
+                 (0,))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -3364,17 +3362,8 @@ class FlatAdamExact(FlatAdam):
     where FlatAdam's f32 `1 - beta^t` leaves up to 6e-7 of every step. FlatAdam itself (and what
     the other learners compute) is unchanged. No weight planes."""
 
-    def write_planes(self, jobs):
-        if list(jobs):
-            raise ValueError("FlatAdamExact writes no weight planes")
-
-    def step(self, grad_scale: float = 1.0):
-        dev = self.params.device
-        call("ocppo_clip_adam_step_exact", _stream(dev), self.params.data_ptr(),
-             self.grads.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-             self.numel, self.lr.data_ptr(), self.betas[0], self.betas[1], self.eps,
-             float(grad_scale), self.max_grad_norm, self.scalars.data_ptr(), self.ws.data_ptr(),
-             self.ws.numel())
+    ENTRY = "ocppo_clip_adam_step_exact"
+    NO_PLANES = ("FlatAdamExact writes no weight planes", ())
 
 
 class SacTemperature:

@@ -896,26 +896,102 @@ def test_replay_buffer_semantics(ops, dev, dt):
 
 
 def test_clip_adam_abi_scalar_tail(ops, dev):
-    """ocppo_clip_adam_step called through the C ABI with P % 4 != 0 (the scalar tail)."""
+    """The three flat steps (ocppo_clip_adam_step, ocppo_clip_adam_step_exact and
+    ocppo_clip_radam_step share one kernel body) called through the C ABI with P % 4 != 0, which
+    the optimizer classes never do (flat_offsets pads to 64): P = 3 is the scalar tail alone,
+    P = 1027 one full workgroup of float4 groups, one group of a second workgroup and the tail,
+    P = 1003 the size this test had. grad_scale 0.5 and max_norm 0.5 on gradients whose norms
+    alternate around 1: every second step clips. Each entry against the twin and at the tolerance
+    of its own test: Adam against the oracle for 3 steps (test_flat_adam_vs_oracle_bit_level's
+    count), exact Adam against torch.optim.Adam for 4 (test_flat_adam_exact_follows_torch_adam's),
+    RAdam against pqn_util.RAdamRef for 7 (rectified from step 6 on), the last two by the rule of
+    lstm_util.check."""
+    import pqn_util as U
     from oc_cleanrl_amd import _lib
 
-    rng = np.random.default_rng(3)
-    P = 1003
-    p0 = rng.standard_normal(P).astype(np.float32)
-    gr = (rng.standard_normal(P) * 0.1).astype(np.float32)
-    p, g = T(p0, dev), T(gr, dev)
-    m, v = torch.zeros(P, device=dev), torch.zeros(P, device=dev)
-    lr = torch.tensor([1e-3], device=dev)
-    sc = torch.zeros(8, device=dev)
-    ws = torch.zeros(int(_lib.LIB.ocppo_clip_adam_workspace_bytes(P)), dtype=torch.uint8, device=dev)
-    _lib.call("ocppo_clip_adam_step", torch.cuda.current_stream(dev).cuda_stream, p.data_ptr(),
-              g.data_ptr(), m.data_ptr(), v.data_ptr(), P, lr.data_ptr(), 0.9, 0.999, 1e-5, 0.5,
-              0.5, sc.data_ptr(), ws.data_ptr(), ws.numel(), 0, None, None, None, None, None)
-    ep, em, ev, step, total = O.clip_adam_step(p0, gr, np.zeros(P, np.float32),
-                                               np.zeros(P, np.float32), 0, 1e-3, max_norm=0.5,
-                                               grad_scale=0.5)
-    np.testing.assert_allclose(float(sc[1]), total, rtol=1e-5)
-    np.testing.assert_allclose(p.cpu().numpy(), ep, rtol=1e-6, atol=1e-9)
+    scale, max_norm = 0.5, 0.5
+    norms = (0.2, 2.0, 0.3, 5.0, 0.1, 3.0, 0.4)  # before grad_scale: steps 2, 4 and 6 clip
+
+    def run(entry, p0, grads, lr, eps, tail, each=None):
+        P = p0.size
+        p, m, v = T(p0, dev), torch.zeros(P, device=dev), torch.zeros(P, device=dev)
+        lrt, sc = torch.tensor([lr], device=dev), torch.zeros(8, device=dev)
+        ws = torch.zeros(int(_lib.LIB.ocppo_clip_adam_workspace_bytes(P)), dtype=torch.uint8,
+                         device=dev)
+        for gr in grads:
+            g = T(gr, dev)
+            _lib.call(entry, torch.cuda.current_stream(dev).cuda_stream, p.data_ptr(),
+                      g.data_ptr(), m.data_ptr(), v.data_ptr(), P, lrt.data_ptr(), 0.9, 0.999, eps,
+                      scale, max_norm, sc.data_ptr(), ws.data_ptr(), ws.numel(), *tail)
+            if each is not None:
+                each(p, sc)
+        return p.cpu(), m.cpu(), v.cpu(), sc.cpu()
+
+    def torch_twin(make, grads, p0, dtype):
+        """Clipped steps of make(p) -> (step(grad), state()) on a `dtype` CPU copy of p0."""
+        p = torch.from_numpy(p0).to(dtype).clone()
+        step, state = make(p)
+        for gr in grads:
+            g = torch.from_numpy(gr).to(dtype) * scale
+            c, _ = U.clip_coef([g], max_norm)
+            step(g * c)
+        return (p.detach(),) + tuple(state())
+
+    def adam_twin(lr, eps):
+        def make(p):
+            p.requires_grad_()
+            opt = torch.optim.Adam([p], lr=lr, eps=eps)
+
+            def step(g):
+                p.grad = g
+                opt.step()
+            return step, lambda: (opt.state[p]["exp_avg"], opt.state[p]["exp_avg_sq"])
+        return make
+
+    def radam_twin(lr):
+        def make(p):
+            ref = U.RAdamRef([p], float(np.float32(lr)))
+            return (lambda g: ref.step([g])), lambda: (ref.m[0], ref.v[0])
+        return make
+
+    for P in (3, 1003, 1027):
+        rng = np.random.default_rng(P)
+        p0 = rng.standard_normal(P).astype(np.float32)
+        grads = []
+        for n in norms:
+            gr = rng.standard_normal(P)
+            grads.append((gr * (n / np.linalg.norm(gr))).astype(np.float32))
+
+        # Adam: the oracle's f32 restatement, step by step
+        ref = dict(p=p0, m=np.zeros(P, np.float32), v=np.zeros(P, np.float32), step=0)
+        seen = []
+
+        def against_oracle(p, sc):
+            gr = grads[ref["step"]]
+            ref["p"], ref["m"], ref["v"], ref["step"], total = O.clip_adam_step(
+                ref["p"], gr, ref["m"], ref["v"], ref["step"], 1e-3, max_norm=max_norm,
+                grad_scale=scale)
+            seen.append(float(sc[2]) < 1.0)
+            np.testing.assert_allclose(float(sc[1]), total, rtol=1e-5)
+            np.testing.assert_allclose(p.cpu().numpy(), ref["p"], rtol=1e-6, atol=1e-9)
+
+        run("ocppo_clip_adam_step", p0, grads[:3], 1e-3, 1e-5, (0, None, None, None, None, None),
+            against_oracle)
+        assert seen == [False, True, False]  # the clip was active where it was meant to be
+
+        # exact Adam and RAdam: torch's computation in f32 and its f64 twin
+        for entry, steps, lr, eps, tail, make in (
+                ("ocppo_clip_adam_step_exact", 4, 3e-4, 1e-4, (), adam_twin(3e-4, 1e-4)),
+                ("ocppo_clip_radam_step", 7, 1e-2, 1e-8, (0,), radam_twin(1e-2))):
+            got = run(entry, p0, grads[:steps], lr, eps, tail)
+            f32 = torch_twin(make, grads[:steps], p0, torch.float32)
+            f64 = torch_twin(make, grads[:steps], p0, torch.float64)
+            for name, a, b, c in zip(("param", "exp_avg", "exp_avg_sq"), got, f32, f64):
+                U.check(f"{entry} P={P} {name}", a, b, c)
+            sc = got[3]
+            assert float(sc[0]) == steps and bool(torch.isfinite(sc).all())
+            if entry == "ocppo_clip_radam_step":
+                assert float(sc[5]) > 0  # the last steps were rectified
 
 
 # ---------------------------------------------------------------------------------------------
