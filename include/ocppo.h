@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCPPO_ABI_VERSION 36
+#define OCPPO_ABI_VERSION 37
 
 /* status codes */
 #define OCPPO_OK 0
@@ -1434,6 +1434,78 @@ OCPPO_API int ocppo_sac_actor_alpha_fwd_bwd(ocppo_stream_t stream, const float* 
 OCPPO_API int ocppo_sac_act(ocppo_stream_t stream, const float* logits, int64_t E, int64_t A,
                             uint64_t seed, const int64_t* step, int64_t step_offset,
                             int64_t learning_starts, int64_t* actions);
+
+/* -------------------------------------------------------------------------------------------
+ * Random Network Distillation (cleanrl/ppo_rnd_envpool.py) beyond PPO (ABI 37). Every entry is
+ * capture-safe (device scalars only), deterministic (no atomics; sums in an order the shapes fix)
+ * and checks its arguments before any launch.
+ *
+ * Running statistics (gym's RunningMeanStd, all f64): state [2C + 1] = mean [C], var [C], count,
+ * starting at zeros, ones, 1e-4. ocppo_rms_update merges the per-column batch mean and population
+ * variance of x [R, C] (dtype OCPPO_F32 / BF16 / U8, rows row_stride elements apart: a frame of a
+ * stacked observation) with batch count R:
+ *   delta = bm - mean; tot = count + R; mean' = mean + delta * R / tot;
+ *   var' = (var * count + bv * R + delta^2 * count * R / tot) / tot; count' = tot.
+ * The column sums are carried as hi + lo pairs, so bm and bv are within an ulp of exact. Two
+ * launches (partials over column blocks x row chunks, then the merge).
+ * ocppo_rnd_normalize: out [R, C] f32 = f32(clip((f64(x) - mean_c) / sqrt(var_c), -5, 5)).
+ *
+ * ocppo_rnd_error: out[r] = sum_j (target[r, j] - pred[r, j])^2 / 2 (:373), rows [R, D].
+ *
+ * ocppo_rnd_reward_norm (:390-400): the RewardForwardFilter over curiosity [T, N] walked along the
+ * env axis as the script does: for n = 0 .. N-1: rewems[t] = rewems[t] * f32(int_gamma) +
+ * curiosity[t, n] (f32, two roundings), filtered[n, t] = rewems[t] (written when filtered is
+ * given); rewems [T] persists (zeros at first). The mean and population variance of the N * T
+ * filtered values (f64, pairs) are merged into state [3] = {mean, var, count} with batch count N
+ * (the script's len() of a 2-D array), then curiosity /= f32(sqrt(var')) in place. Two launches.
+ *
+ * ocppo_rnd_gae (:406-442): both scans in one launch, each op for op ocppo_gae's arithmetic and so
+ * bitwise the script's f32 loop: extrinsic over rewards / ext_values / dones with gamma, intrinsic
+ * over curiosity / int_values with int_gamma and nonterminal 1; returns = advantages + values;
+ * advantages = (int_adv * f32(int_coef)) + (ext_adv * f32(ext_coef)). All arrays [T, N] f32, the
+ * next_* rows [N].
+ *
+ * ocppo_rnd_aux_loss_fwd_bwd (:463-472, :509): with d = pred - target [M, D], row loss
+ * f_r = mean_j d^2, mask_r = unit53(splitmix64(h + r + 1)) < update_proportion where
+ * h = splitmix64(splitmix64(seed ^ key) + *counter) (the library's counter stream, not torch.rand),
+ * c = max(sum mask, 1):  dpred = d * f32(2 / (D c)) on kept rows, d * 0 elsewhere;
+ * dv_int = (v_int - ret_int) * f32(vf_coef / M); stats [3] = {0.5 mean (v_int - ret_int)^2,
+ * sum_r mask_r f_r / c, sum mask} (batch sums in f64). *counter advances by one (on the device, in
+ * the second of its two launches). update_proportion outside [0, 1] is refused.
+ * ocppo_rnd_mask writes the same mask [M] as f32 0 / 1 for *counter, which it leaves alone.
+ *
+ * Workspaces: ocppo_*_workspace_bytes, 8-byte aligned, no initial contents needed.
+ * ------------------------------------------------------------------------------------------- */
+OCPPO_API size_t ocppo_rms_update_workspace_bytes(int64_t R, int64_t C);
+OCPPO_API int ocppo_rms_update(ocppo_stream_t stream, const void* x, int dtype, int64_t R,
+                               int64_t C, int64_t row_stride, double* state, void* workspace,
+                               size_t workspace_bytes);
+OCPPO_API int ocppo_rnd_normalize(ocppo_stream_t stream, const void* x, int dtype, int64_t R,
+                                  int64_t C, int64_t row_stride, const double* state, float* out);
+OCPPO_API int ocppo_rnd_error(ocppo_stream_t stream, const float* pred, const float* target,
+                              int64_t R, int64_t D, float* out);
+OCPPO_API size_t ocppo_rnd_reward_norm_workspace_bytes(int64_t T);
+OCPPO_API int ocppo_rnd_reward_norm(ocppo_stream_t stream, float* curiosity, float* rewems,
+                                    double* state, int64_t T, int64_t N, double int_gamma,
+                                    void* workspace, size_t workspace_bytes, float* filtered);
+OCPPO_API int ocppo_rnd_gae(ocppo_stream_t stream, const float* rewards, const float* ext_values,
+                            const float* dones, const float* next_ext_value,
+                            const float* next_done, const float* curiosity,
+                            const float* int_values, const float* next_int_value, int64_t T,
+                            int64_t N, double gamma, double int_gamma, double gae_lambda,
+                            double int_coef, double ext_coef, float* ext_advantages,
+                            float* ext_returns, float* int_advantages, float* int_returns,
+                            float* advantages);
+OCPPO_API size_t ocppo_rnd_aux_loss_workspace_bytes(int64_t M);
+OCPPO_API int ocppo_rnd_aux_loss_fwd_bwd(ocppo_stream_t stream, const float* pred,
+                                         const float* target, const float* v_int,
+                                         const float* ret_int, int64_t M, int64_t D,
+                                         uint64_t seed, int64_t* counter,
+                                         double update_proportion, double vf_coef, float* dpred,
+                                         float* dv_int, float* stats, void* workspace,
+                                         size_t workspace_bytes);
+OCPPO_API int ocppo_rnd_mask(ocppo_stream_t stream, uint64_t seed, const int64_t* counter,
+                             int64_t M, double update_proportion, float* out);
 
 #ifdef __cplusplus
 }

@@ -22,7 +22,7 @@ LIB_PATH = Path(os.environ.get("OCPPO_LIB", PKG / "lib" / "libocppo_hip.so"))
 HEADER = PKG.parent / "include" / "ocppo.h"
 
 # constants mirrored from include/ocppo.h (checked against the header by tests/test_abi.py)
-OCPPO_ABI_VERSION = 36
+OCPPO_ABI_VERSION = 37
 OCPPO_OK, OCPPO_E_INVALID, OCPPO_E_LAUNCH, OCPPO_E_WORKSPACE = 0, 1, 2, 3
 OCPPO_F32, OCPPO_BF16, OCPPO_U8 = 0, 1, 2
 OCPPO_X6_MBITS_ROWS = 2
@@ -168,6 +168,16 @@ SIGNATURES: dict[str, tuple[type, list]] = {
                                           P, P]),
     "ocppo_sac_act": (I, [P, P, I64, I64, U64, P, I64, I64, P]),
     "ocppo_clip_adam_step_exact": (I, [P, P, P, P, P, I64, P, D, D, D, D, D, P, P, SZ]),
+    "ocppo_rms_update_workspace_bytes": (SZ, [I64, I64]),
+    "ocppo_rms_update": (I, [P, P, I, I64, I64, I64, P, P, SZ]),
+    "ocppo_rnd_normalize": (I, [P, P, I, I64, I64, I64, P, P]),
+    "ocppo_rnd_error": (I, [P, P, P, I64, I64, P]),
+    "ocppo_rnd_reward_norm_workspace_bytes": (SZ, [I64]),
+    "ocppo_rnd_reward_norm": (I, [P, P, P, P, I64, I64, D, P, SZ, P]),
+    "ocppo_rnd_gae": (I, [P, P, P, P, P, P, P, P, P, I64, I64, D, D, D, D, D, P, P, P, P, P]),
+    "ocppo_rnd_aux_loss_workspace_bytes": (SZ, [I64]),
+    "ocppo_rnd_aux_loss_fwd_bwd": (I, [P, P, P, P, P, I64, I64, U64, P, D, D, P, P, P, P, SZ]),
+    "ocppo_rnd_mask": (I, [P, U64, P, I64, D, P]),
 }
 
 

@@ -3406,3 +3406,172 @@ def sac_actor_alpha_fwd_bwd(logits, q1, q2, temp: SacTemperature, dlogits=None, 
          temp.betas[1], temp.eps, int(temp.autotune), _check(dlogits, "dlogits", f, dev, n),
          _check(stats, "stats", f, dev, 4))
     return stats, dlogits
+
+
+# ---------------------------------------------------------------------------------------------
+# Random Network Distillation (ppo_rnd_envpool.py): running statistics, normalisation, curiosity,
+# reward filter, both GAE scans, intrinsic value + masked forward loss (csrc/ocppo_rnd.hip)
+# ---------------------------------------------------------------------------------------------
+def rms_state(C: int, device):
+    """gym's RunningMeanStd(shape=[C]) on the device: f64 [2C + 1] = mean (zeros), var (ones),
+    count (1e-4)."""
+    st = torch.zeros(2 * C + 1, dtype=torch.float64, device=device)
+    st[C:2 * C] = 1.0
+    st[2 * C] = 1e-4
+    return st
+
+
+def _rows2d(x, name: str):
+    """(pointer, dtype code, R, C, row stride) of x [R, C] f32 / bf16 / u8 on the GPU whose rows
+    are contiguous and a fixed number of elements apart (a frame of a stacked observation)."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.device.type != "cuda":
+        raise ValueError(f"{name}: expected a GPU tensor [R, C], got "
+                         f"{tuple(getattr(x, 'shape', ()))} on {getattr(x, 'device', None)}")
+    if x.dtype not in _DTYPE_CODE:
+        raise ValueError(f"{name}: dtype {x.dtype}, expected float32, bfloat16 or uint8")
+    R, C = x.shape
+    if R < 1 or C < 1:
+        raise ValueError(f"{name}: empty [{R}, {C}]")
+    ld = x.stride(0) if R > 1 else C
+    if (C > 1 and x.stride(1) != 1) or ld < C:
+        raise ValueError(f"{name}: rows must be contiguous and at least C elements apart, got "
+                         f"strides {x.stride()}")
+    return x.data_ptr(), _DTYPE_CODE[x.dtype], R, C, ld
+
+
+def _rnd_ws(tag: str, dev, nbytes: int):
+    return _persistent(tag, dev, nbytes, lambda: torch.empty(
+        max(nbytes // 8, 1), dtype=torch.float64, device=dev))
+
+
+def rms_update(x, state):
+    """gym's RunningMeanStd.update(x) on the device state [2C + 1] f64 (rms_state): the per-column
+    batch mean and population variance of x [R, C] (f32 / bf16 / u8, rows possibly strided) merged
+    with count R (ppo_rnd_envpool.py:333, :444). Two launches."""
+    px, code, R, C, ld = _rows2d(x, "rms_update: x")
+    dev = x.device
+    nb = int(_lib.LIB.ocppo_rms_update_workspace_bytes(R, C))
+    ws = _rnd_ws("rms_update", dev, nb)
+    call("ocppo_rms_update", _stream(dev), px, code, R, C, ld,
+         _check(state, "state", torch.float64, dev, 2 * C + 1), ws.data_ptr(), ws.numel() * 8)
+    return state
+
+
+def rnd_normalize(x, state, out=None):
+    """((x - mean) / sqrt(var)).clip(-5, 5).float() of ppo_rnd_envpool.py:365-370 / :449-454 with
+    the f64 statistics of rms_update: out [R, C] f32."""
+    px, code, R, C, ld = _rows2d(x, "rnd_normalize: x")
+    dev = x.device
+    if out is None:
+        out = torch.empty((R, C), dtype=torch.float32, device=dev)
+    call("ocppo_rnd_normalize", _stream(dev), px, code, R, C, ld,
+         _check(state, "state", torch.float64, dev, 2 * C + 1),
+         _check(out, "out", torch.float32, dev, R * C))
+    return out
+
+
+def rnd_curiosity(pred, target, out=None):
+    """(target - pred).pow(2).sum(1) / 2 of ppo_rnd_envpool.py:373; rows [R, D] f32 -> [R]."""
+    if pred.dim() != 2 or pred.shape[1] < 1:
+        raise ValueError(f"rnd_curiosity: pred must be [R, D >= 1], got {tuple(pred.shape)}")
+    R, D = pred.shape
+    dev, f = pred.device, torch.float32
+    pp = _check(pred, "pred", f)
+    if out is None:
+        out = torch.empty(R, dtype=f, device=dev)
+    call("ocppo_rnd_error", _stream(dev), pp, _check(target, "target", f, dev, R * D), R, D,
+         _check(out, "out", f, dev, R))
+    return out
+
+
+def rnd_reward_norm(curiosity, rewems, state, int_gamma: float, filtered=None):
+    """ppo_rnd_envpool.py:390-400 in two launches: the RewardForwardFilter over curiosity [T, N]
+    along the env axis (rewems [T] f32 carried across calls, zeros at first), the filtered values'
+    mean and population variance merged into state [3] f64 = {mean, var, count} with count N, and
+    curiosity /= f32(sqrt(var)) in place. filtered [N, T], if given, receives the filter output."""
+    if curiosity.dim() != 2:
+        raise ValueError(f"rnd_reward_norm: curiosity must be [T, N], got {tuple(curiosity.shape)}")
+    T, N = curiosity.shape
+    dev, f = curiosity.device, torch.float32
+    pc = _check(curiosity, "curiosity", f)
+    nb = int(_lib.LIB.ocppo_rnd_reward_norm_workspace_bytes(T))
+    ws = _rnd_ws("rnd_reward_norm", dev, nb)
+    call("ocppo_rnd_reward_norm", _stream(dev), pc, _check(rewems, "rewems", f, dev, T),
+         _check(state, "state", torch.float64, dev, 3), T, N, float(int_gamma), ws.data_ptr(),
+         ws.numel() * 8, _opt(filtered, "filtered", f, dev, T * N))
+    return curiosity
+
+
+def rnd_gae(rewards, ext_values, dones, next_ext_value, next_done, curiosity, int_values,
+            next_int_value, gamma: float, int_gamma: float, gae_lambda: float, int_coef: float,
+            ext_coef: float, ext_advantages=None, ext_returns=None, int_advantages=None,
+            int_returns=None, advantages=None):
+    """Both GAE scans of ppo_rnd_envpool.py:406-430 and the combined advantage of :442 in one
+    launch, bitwise the script's f32 loop: [T, N] f32 in, (ext_adv, ext_ret, int_adv, int_ret,
+    adv = int_adv * int_coef + ext_adv * ext_coef) out."""
+    if rewards.dim() != 2:
+        raise ValueError(f"rnd_gae: rewards must be [T, N], got {tuple(rewards.shape)}")
+    T, N = rewards.shape
+    dev, f = rewards.device, torch.float32
+    outs = [torch.empty_like(rewards) if o is None else o
+            for o in (ext_advantages, ext_returns, int_advantages, int_returns, advantages)]
+    names = ("ext_advantages", "ext_returns", "int_advantages", "int_returns", "advantages")
+    call("ocppo_rnd_gae", _stream(dev), _check(rewards, "rewards", f, dev),
+         _check(ext_values, "ext_values", f, dev, T * N), _check(dones, "dones", f, dev, T * N),
+         _check(next_ext_value, "next_ext_value", f, dev, N),
+         _check(next_done, "next_done", f, dev, N),
+         _check(curiosity, "curiosity", f, dev, T * N),
+         _check(int_values, "int_values", f, dev, T * N),
+         _check(next_int_value, "next_int_value", f, dev, N), T, N, float(gamma),
+         float(int_gamma), float(gae_lambda), float(int_coef), float(ext_coef),
+         *[_check(o, n, f, dev, T * N) for o, n in zip(outs, names)])
+    return tuple(outs)
+
+
+RND_STAT_NAMES = ("int_v_loss", "fwd_loss", "mask_count")
+
+
+def rnd_mask_counter(device):
+    """The device minibatch counter of the update mask's stream (i64 [1], zero)."""
+    return torch.zeros(1, dtype=torch.int64, device=device)
+
+
+def rnd_aux_loss_fwd_bwd(pred, target, v_int, ret_int, seed: int, counter,
+                         update_proportion: float, vf_coef: float, dpred=None, dv_int=None,
+                         stats=None):
+    """The intrinsic value loss and the masked forward loss of ppo_rnd_envpool.py:463-472, :509
+    with their gradients: dpred [M, D] = d loss / d pred, dv_int [M] = vf_coef * d int_v_loss /
+    d v_int, stats [3] = RND_STAT_NAMES. The mask is the library's counter stream keyed by (seed,
+    counter, row); counter (rnd_mask_counter) advances by one on the device. Two launches."""
+    if pred.dim() != 2 or pred.shape[0] < 1 or pred.shape[1] < 1:
+        raise ValueError(f"rnd_aux_loss_fwd_bwd: pred must be [M >= 1, D >= 1], got "
+                         f"{tuple(pred.shape)}")
+    M, D = pred.shape
+    dev, f = pred.device, torch.float32
+    pp = _check(pred, "pred", f)
+    if dpred is None:
+        dpred = torch.empty_like(pred)
+    if dv_int is None:
+        dv_int = torch.empty(M, dtype=f, device=dev)
+    if stats is None:
+        stats = torch.empty(3, dtype=f, device=dev)
+    nb = int(_lib.LIB.ocppo_rnd_aux_loss_workspace_bytes(M))
+    ws = _rnd_ws("rnd_aux_loss_fwd_bwd", dev, nb)
+    call("ocppo_rnd_aux_loss_fwd_bwd", _stream(dev), pp, _check(target, "target", f, dev, M * D),
+         _check(v_int, "v_int", f, dev, M), _check(ret_int, "ret_int", f, dev, M), M, D,
+         int(seed) & 0xFFFFFFFFFFFFFFFF, _check(counter, "counter", torch.int64, dev, 1),
+         float(update_proportion), float(vf_coef), _check(dpred, "dpred", f, dev, M * D),
+         _check(dv_int, "dv_int", f, dev, M), _check(stats, "stats", f, dev, 3), ws.data_ptr(),
+         ws.numel() * 8)
+    return stats, dpred, dv_int
+
+
+def rnd_mask(seed: int, counter, M: int, update_proportion: float, out=None):
+    """The update mask rnd_aux_loss_fwd_bwd applies at `counter` (left as it is): f32 0 / 1 [M]."""
+    dev = counter.device
+    if out is None:
+        out = torch.empty(M, dtype=torch.float32, device=dev)
+    call("ocppo_rnd_mask", _stream(dev), int(seed) & 0xFFFFFFFFFFFFFFFF,
+         _check(counter, "counter", torch.int64, dev, 1), M, float(update_proportion),
+         _check(out, "out", torch.float32, dev, M))
+    return out
