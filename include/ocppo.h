@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCPPO_ABI_VERSION 37
+#define OCPPO_ABI_VERSION 38
 
 /* status codes */
 #define OCPPO_OK 0
@@ -1506,6 +1506,59 @@ OCPPO_API int ocppo_rnd_aux_loss_fwd_bwd(ocppo_stream_t stream, const float* pre
                                          size_t workspace_bytes);
 OCPPO_API int ocppo_rnd_mask(ocppo_stream_t stream, uint64_t seed, const int64_t* counter,
                              int64_t M, double update_proportion, float* out);
+
+/* -------------------------------------------------------------------------------------------
+ * Phasic Policy Gradient (cleanrl/ppg_procgen.py) beyond PPO (ABI 38). Every entry is capture-safe,
+ * deterministic (no atomics; sums in an order the sizes fix) and checks its arguments before any
+ * launch.
+ *
+ * ocppo_ppg_aux_loss_fwd_bwd (:449-461), rows [M], 1 <= A <= 18: per row both logit rows are
+ * normalised as Categorical(logits=..) normalises them (the loss and rollout kernels' routine):
+ *   kl_r = sum_j p_old_j (ln_old_j - ln_new_j)   (a term with p_old_j == 0 counts 0, one with
+ *          p_new_j == 0 and p_old_j != 0 counts +inf: torch.distributions.kl's masks)
+ *   dlogits = (p_new - p_old) * f32(beta_clone / M)   (d (beta_clone mean kl) / d new_logits)
+ *   dvalue = (new_value - returns) * f32(1 / M); daux = (new_aux_value - returns) * f32(1 / M)
+ *   stats [3] = {mean kl_r, 0.5 mean (new_aux_value - returns)^2, 0.5 mean (new_value - returns)^2}
+ * (row sums in f64). A row whose old and new logits are bit-equal gives kl_r == 0 and a zero
+ * dlogits row exactly. Two launches; workspace ocppo_ppg_aux_loss_workspace_bytes(M), 8-byte
+ * aligned, no initial contents needed.
+ *
+ * ocppo_ppg_aux_gather (:443-453): one launch writes the auxiliary minibatch of the env columns
+ * cols [k] (int64, device) of aux_obs [T, R, D] (obs_dtype OCPPO_F32 / BF16 / U8), aux_pi [T, R, A]
+ * f32 and aux_returns [T, R] f32, flattened t-major: output row t k + c holds column cols[c] of
+ * step t; out_obs [T k, D] f32 (the exact conversion ocppo_gather_rows makes), out_pi [T k, A],
+ * out_returns [T k]. 16-byte stores where D (A) % 4 == 0 and the pointers are aligned. A column
+ * index outside [0, R) is never dereferenced: it is clamped into the range.
+ *
+ * ocppo_clip_adam_step_seg: ocppo_clip_adam_step (same arithmetic, same scalars and workspace, no
+ * plane jobs) over a buffer of two segments, the head [0, split) and the tail [split, P) (split and
+ * P multiples of 4), each with its own step count, as torch.optim.Adam keeps one per parameter and
+ * skips a parameter whose grad is None. The head takes part in every step; its count is
+ * scalars[OCPPO_OPT_STEP]. tail_active = 0: the clip norm runs over the head's gradients alone and
+ * nothing of the tail -- parameters, both moments, scalars[OCPPO_OPT_TAIL_STEP] -- is written or
+ * read; scalars[OCPPO_OPT_TAIL_SKIPPED] counts these steps. tail_active = 1: the norm runs over
+ * the whole buffer and the tail's step scalars are formed from its own count,
+ * OCPPO_OPT_STEP - OCPPO_OPT_TAIL_SKIPPED, which scalars[OCPPO_OPT_TAIL_STEP] then reports.
+ * ------------------------------------------------------------------------------------------- */
+#define OCPPO_OPT_TAIL_SKIPPED 6
+#define OCPPO_OPT_TAIL_STEP 7
+OCPPO_API size_t ocppo_ppg_aux_loss_workspace_bytes(int64_t M);
+OCPPO_API int ocppo_ppg_aux_loss_fwd_bwd(ocppo_stream_t stream, const float* new_logits,
+                                         const float* new_value, const float* new_aux_value,
+                                         const float* old_logits, const float* returns, int64_t M,
+                                         int64_t A, double beta_clone, float* dlogits,
+                                         float* dvalue, float* daux, float* stats,
+                                         void* workspace, size_t workspace_bytes);
+OCPPO_API int ocppo_ppg_aux_gather(ocppo_stream_t stream, const void* aux_obs, int obs_dtype,
+                                   const float* aux_pi, const float* aux_returns,
+                                   const int64_t* cols, int64_t T, int64_t R, int64_t k, int64_t D,
+                                   int64_t A, float* out_obs, float* out_pi, float* out_returns);
+OCPPO_API int ocppo_clip_adam_step_seg(ocppo_stream_t stream, float* params, const float* grads,
+                                       float* exp_avg, float* exp_avg_sq, int64_t P, int64_t split,
+                                       int tail_active, const float* lr, double beta1,
+                                       double beta2, double eps, double grad_scale,
+                                       double max_norm, float* scalars, void* workspace,
+                                       size_t workspace_bytes);
 
 #ifdef __cplusplus
 }

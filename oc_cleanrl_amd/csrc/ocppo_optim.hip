@@ -21,6 +21,9 @@
 // doubles) and ocppo_clip_radam_step (torch.optim.RAdam): one norm kernel, one step kernel
 // (flat_step_kernel) instantiated with the rule that supplies the step scalars and the
 // per-element update, one host helper (flat_step) behind the three entries.
+// ocppo_clip_adam_step_seg (a head and a tail segment with a step count each, the tail optional
+// per step) runs the same norm kernel over the active length and flat_step_seg_kernel, the same
+// loop with the rule's scalars taken once per segment.
 #include "ocppo_common.h"
 #include "ocppo_x6split.h"
 
@@ -313,6 +316,68 @@ __global__ __launch_bounds__(kOptThreads) void flat_step_kernel(
       Rule::elem(p[j], (g[j] * grad_scale) * sc.clip, m[j], v[j], sc, eps);
 }
 
+// The step over a buffer of two segments, a head [0, split) and a tail [split, P), each with its
+// own step count (ocppo_clip_adam_step_seg): the same loop, Rule::scalars once per segment from that
+// segment's count and Rule::elem with the scalars of the segment an element group lies in (split
+// and P are multiples of 4, so no group straddles). The head's count is the norm pass's S_STEP. The
+// tail's is S_STEP - S_TAIL_SKIPPED: a step that leaves the tail out adds one to S_TAIL_SKIPPED
+// (workgroup 0, which is the only one to read it in that launch) and touches nothing else of the
+// tail -- the loop ends at split; a step that takes it in reads both counts, written by earlier
+// launches only, and reports the tail's in S_TAIL_STEP.
+enum { S_TAIL_SKIPPED = 6, S_TAIL_STEP = 7 };
+
+template <class Rule>
+__global__ __launch_bounds__(kOptThreads) void flat_step_seg_kernel(
+    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+    float* __restrict__ v, int64_t P, int64_t split, int tail_active, float grad_scale, double b1,
+    double b2, float eps, float max_norm, const float* __restrict__ lr,
+    const float* __restrict__ partials, int nb, float* __restrict__ scalars) {
+  __shared__ typename Rule::Scalars sc_lds[2];
+  const int64_t P4 = (tail_active ? P : split) / 4, split4 = split / 4;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * kOptThreads;
+  int64_t i = static_cast<int64_t>(blockIdx.x) * kOptThreads + threadIdx.x;
+  float4 pp{}, gg{}, mm{}, vv{};
+  if (i < P4) {
+    pp = reinterpret_cast<float4*>(p)[i];
+    gg = reinterpret_cast<const float4*>(g)[i];
+    mm = reinterpret_cast<float4*>(m)[i];
+    vv = reinterpret_cast<float4*>(v)[i];
+  }
+  const NormClip nc = norm_clip(partials, nb, max_norm);
+  if (threadIdx.x == 0) {
+    const float step = scalars[S_STEP];
+    sc_lds[0] = Rule::scalars(nc, step, lr[0], b1, b2);
+    float tail_step = 1.f;  // unused when the tail is left out
+    if (tail_active) tail_step = step - scalars[S_TAIL_SKIPPED];
+    sc_lds[1] = Rule::scalars(nc, tail_step, lr[0], b1, b2);
+    if (blockIdx.x == 0) {
+      scalars[S_TOTAL_NORM] = nc.total;
+      scalars[S_CLIP] = nc.clip;
+      Rule::report(sc_lds[0], scalars);
+      if (tail_active) scalars[S_TAIL_STEP] = tail_step;
+      else scalars[S_TAIL_SKIPPED] = scalars[S_TAIL_SKIPPED] + 1.f;
+    }
+  }
+  __syncthreads();
+  const typename Rule::Scalars sh = sc_lds[0], st = sc_lds[1];
+  for (; i < P4; i += stride) {
+    const typename Rule::Scalars& sc = i >= split4 ? st : sh;
+    Rule::elem(pp.x, (gg.x * grad_scale) * sc.clip, mm.x, vv.x, sc, eps);
+    Rule::elem(pp.y, (gg.y * grad_scale) * sc.clip, mm.y, vv.y, sc, eps);
+    Rule::elem(pp.z, (gg.z * grad_scale) * sc.clip, mm.z, vv.z, sc, eps);
+    Rule::elem(pp.w, (gg.w * grad_scale) * sc.clip, mm.w, vv.w, sc, eps);
+    reinterpret_cast<float4*>(p)[i] = pp;
+    reinterpret_cast<float4*>(m)[i] = mm;
+    reinterpret_cast<float4*>(v)[i] = vv;
+    if (i + stride < P4) {
+      pp = reinterpret_cast<float4*>(p)[i + stride];
+      gg = reinterpret_cast<const float4*>(g)[i + stride];
+      mm = reinterpret_cast<float4*>(m)[i + stride];
+      vv = reinterpret_cast<float4*>(v)[i + stride];
+    }
+  }
+}
+
 constexpr size_t kOptWorkspaceBytes = 256 + kOptBlocks * sizeof(float);
 
 // What the three entries share once their own size and plane arguments are through: the checks,
@@ -407,6 +472,49 @@ extern "C" int ocppo_clip_adam_step_exact(ocppo_stream_t stream, float* params,
   return flat_step<AdamExactRule>("ocppo_clip_adam_step_exact", stream, params, grads, exp_avg,
                                   exp_avg_sq, P, lr, beta1, beta2, eps, grad_scale, max_norm,
                                   scalars, workspace, workspace_bytes, AdamPlanes{});
+}
+
+extern "C" int ocppo_clip_adam_step_seg(ocppo_stream_t stream, float* params, const float* grads,
+                                        float* exp_avg, float* exp_avg_sq, int64_t P,
+                                        int64_t split, int tail_active, const float* lr,
+                                        double beta1, double beta2, double eps,
+                                        double grad_scale, double max_norm, float* scalars,
+                                        void* workspace, size_t workspace_bytes) {
+  const char* who = "ocppo_clip_adam_step_seg";
+  OCPPO_REQUIRE(P > 0 && split > 0 && split < P && P % 4 == 0 && split % 4 == 0,
+                "%s: bad sizes P=%lld split=%lld (0 < split < P, both multiples of 4)", who,
+                (long long)P, (long long)split);
+  OCPPO_REQUIRE(tail_active == 0 || tail_active == 1, "%s: tail_active=%d is not 0 / 1", who,
+                tail_active);
+  OCPPO_REQUIRE(params && grads && exp_avg && exp_avg_sq && lr && scalars, "%s: null pointer", who);
+  OCPPO_REQUIRE(beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1,
+                "%s: betas (%g, %g) must be in [0, 1)", who, beta1, beta2);
+  if (!workspace || workspace_bytes < kOptWorkspaceBytes)
+    return fail(OCPPO_E_WORKSPACE, "%s: workspace needs %zu bytes, got %zu", who,
+                kOptWorkspaceBytes, workspace_bytes);
+  OCPPO_REQUIRE((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) |
+                 reinterpret_cast<uintptr_t>(exp_avg) | reinterpret_cast<uintptr_t>(exp_avg_sq)) %
+                        16 == 0,
+                "%s: buffers must be 16-byte aligned", who);
+  float* partials = reinterpret_cast<float*>(static_cast<char*>(workspace) + 256);
+  // the grids of ocppo_clip_adam_step over the whole buffer, whichever segments take part: the
+  // norm pass over the active length alone then sums, thread by thread, what the whole-buffer
+  // pass sums when the left-out gradients are zero (bitwise the same total)
+  const int64_t groups = ceil_div(P / 4, kOptThreads);
+  const int64_t nb = groups < kOptBlocks ? groups : kOptBlocks;
+  const int64_t na = groups < AdamRule::kMaxBlocks ? groups : AdamRule::kMaxBlocks;
+  const int64_t active = tail_active ? P : split;
+  clear_stale_error();
+  hipStream_t s = as_stream(stream);
+  hipLaunchKernelGGL(grad_norm_kernel, dim3(static_cast<unsigned>(nb)), dim3(kOptThreads), 0, s,
+                     grads, active, static_cast<float>(grad_scale), scalars, partials);
+  if (int rc = check_launch("ocppo_clip_adam_step_seg/norm")) return rc;
+  hipLaunchKernelGGL(flat_step_seg_kernel<AdamRule>, dim3(static_cast<unsigned>(na)),
+                     dim3(kOptThreads), 0, s, params, grads, exp_avg, exp_avg_sq, P, split,
+                     tail_active, static_cast<float>(grad_scale), beta1, beta2,
+                     static_cast<float>(eps), static_cast<float>(max_norm), lr, partials,
+                     static_cast<int>(nb), scalars);
+  return check_launch("ocppo_clip_adam_step_seg/step");
 }
 
 extern "C" int ocppo_clip_radam_step(ocppo_stream_t stream, float* params, const float* grads,

@@ -3575,3 +3575,134 @@ def rnd_mask(seed: int, counter, M: int, update_proportion: float, out=None):
          _check(counter, "counter", torch.int64, dev, 1), M, float(update_proportion),
          _check(out, "out", torch.float32, dev, M))
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# Phasic Policy Gradient (ppg_procgen.py): the auxiliary minibatch gather, the auxiliary loss with
+# its three gradients (csrc/ocppo_ppg.hip) and Adam with a step count per segment
+# ---------------------------------------------------------------------------------------------
+PPG_MAX_ACTIONS = 18
+PPG_STAT_NAMES = ("kl_loss", "aux_value_loss", "real_value_loss")
+
+
+def ppg_aux_loss_fwd_bwd(new_logits, new_value, new_aux_value, old_logits, returns,
+                         beta_clone: float, dlogits=None, dvalue=None, daux=None, stats=None):
+    """ppg_procgen.py:449-461 with its gradients: kl_loss = mean KL(Categorical(old_logits) ||
+    Categorical(new_logits)), the two value regressions 0.5 mean (v - returns)^2, and the
+    gradients of aux_value_loss + beta_clone * kl_loss + real_value_loss: dlogits [M, A] =
+    beta_clone / M (p_new - p_old), dvalue [M] = (new_value - returns) / M, daux [M] likewise.
+    Returns (stats [3] = PPG_STAT_NAMES, dlogits, dvalue, daux). Two launches."""
+    if new_logits.dim() != 2 or new_logits.shape[0] < 1 or \
+            not 1 <= new_logits.shape[1] <= PPG_MAX_ACTIONS:
+        raise ValueError(f"ppg_aux_loss_fwd_bwd: new_logits must be [M >= 1, 1 <= A <= "
+                         f"{PPG_MAX_ACTIONS}], got {tuple(new_logits.shape)}")
+    M, A = new_logits.shape
+    dev, f = new_logits.device, torch.float32
+    pl = _check(new_logits, "new_logits", f)
+    if dlogits is None:
+        dlogits = torch.empty_like(new_logits)
+    if dvalue is None:
+        dvalue = torch.empty(M, dtype=f, device=dev)
+    if daux is None:
+        daux = torch.empty(M, dtype=f, device=dev)
+    if stats is None:
+        stats = torch.empty(3, dtype=f, device=dev)
+    nb = int(_lib.LIB.ocppo_ppg_aux_loss_workspace_bytes(M))
+    ws = _persistent("ppg_aux_loss_fwd_bwd", dev, nb, lambda: torch.empty(
+        max(nb // 8, 1), dtype=torch.float64, device=dev))
+    call("ocppo_ppg_aux_loss_fwd_bwd", _stream(dev), pl,
+         _check(new_value, "new_value", f, dev, M),
+         _check(new_aux_value, "new_aux_value", f, dev, M),
+         _check(old_logits, "old_logits", f, dev, M * A), _check(returns, "returns", f, dev, M),
+         M, A, float(beta_clone), _check(dlogits, "dlogits", f, dev, M * A),
+         _check(dvalue, "dvalue", f, dev, M), _check(daux, "daux", f, dev, M),
+         _check(stats, "stats", f, dev, 3), ws.data_ptr(), ws.numel() * 8)
+    return stats, dlogits, dvalue, daux
+
+
+def ppg_aux_gather(aux_obs, aux_pi, aux_returns, cols, out_obs=None, out_pi=None,
+                   out_returns=None):
+    """The auxiliary minibatch of ppg_procgen.py:443-453 in one launch: flatten01(aux_*[:, cols])
+    of aux_obs [T, R, ...] (f32 / bf16 / u8, converted exactly to f32), aux_pi [T, R, A] f32 and
+    aux_returns [T, R] f32 -> (out_obs [T k, ...], out_pi [T k, A], out_returns [T k]), rows t
+    major. cols: k column indices, an int64 device tensor (graph replays read it afresh; an index
+    outside [0, R) is clamped into the range by the kernel, never dereferenced) or a host
+    list, which is checked here and refused when out of range."""
+    if aux_obs.dim() < 3 or aux_pi.dim() != 3 or aux_returns.dim() != 2:
+        raise ValueError("ppg_aux_gather: aux_obs [T, R, ...], aux_pi [T, R, A], aux_returns [T, R]")
+    T, R = aux_obs.shape[:2]
+    A = aux_pi.shape[2]
+    D = aux_obs[0, 0].numel() if T and R else 0
+    dev, f = aux_obs.device, torch.float32
+    if aux_obs.dtype not in _DTYPE_CODE:
+        raise ValueError(f"ppg_aux_gather: unsupported aux_obs dtype {aux_obs.dtype}")
+    if tuple(aux_pi.shape[:2]) != (T, R) or tuple(aux_returns.shape) != (T, R) or \
+            min(T, R, A, D) < 1:
+        raise ValueError(f"ppg_aux_gather: shapes {tuple(aux_obs.shape)}, {tuple(aux_pi.shape)}, "
+                         f"{tuple(aux_returns.shape)} do not agree on [T >= 1, R >= 1]")
+    if not isinstance(cols, torch.Tensor):
+        cols = [int(c) for c in cols]
+        bad = [c for c in cols if not 0 <= c < R]
+        if bad:
+            raise IndexError(f"ppg_aux_gather: column indices {bad} outside [0, {R})")
+        cols = torch.tensor(cols, dtype=torch.int64, device=dev)
+    k = cols.numel()
+    if k < 1:
+        raise ValueError("ppg_aux_gather: no columns")
+    if out_obs is None:
+        out_obs = torch.empty((T * k,) + tuple(aux_obs.shape[2:]), dtype=f, device=dev)
+    if out_pi is None:
+        out_pi = torch.empty((T * k, A), dtype=f, device=dev)
+    if out_returns is None:
+        out_returns = torch.empty(T * k, dtype=f, device=dev)
+    call("ocppo_ppg_aux_gather", _stream(dev), _check(aux_obs, "aux_obs", None, dev),
+         _DTYPE_CODE[aux_obs.dtype], _check(aux_pi, "aux_pi", f, dev),
+         _check(aux_returns, "aux_returns", f, dev), _check(cols, "cols", torch.int64, dev, k),
+         T, R, k, D, A, _check(out_obs, "out_obs", f, dev, T * k * D),
+         _check(out_pi, "out_pi", f, dev, T * k * A),
+         _check(out_returns, "out_returns", f, dev, T * k))
+    return out_obs, out_pi, out_returns
+
+
+OPT_TAIL_SKIPPED, OPT_TAIL_STEP = 6, 7
+
+
+class FlatAdamSegments(FlatAdam):
+    """FlatAdam over a flat buffer of two segments -- `params` (the head) followed by
+    `tail_params` -- each with its own device step count, as torch.optim.Adam keeps one per
+    parameter and skips a parameter whose grad is None (ocppo_clip_adam_step_seg).
+    step(tail_active=False): the clip norm runs over the head's gradients alone and the tail's
+    parameters, moments and step count are neither read nor written; step(True): one clip over
+    both, each segment's step scalars formed from its own count exactly as FlatAdam forms them.
+    scalars[OPT_STEP] is the head's count, scalars[OPT_TAIL_STEP] the tail's (as of its last
+    step), scalars[OPT_TAIL_SKIPPED] the steps the tail sat out. No weight planes: a trainer
+    refreshes them with ops.WeightPlanes.refresh per minibatch."""
+
+    ENTRY = "ocppo_clip_adam_step_seg"
+    NO_PLANES = ("FlatAdamSegments writes no weight planes (ocppo_clip_adam_step_seg takes no "
+                 "plane jobs)", ())
+
+    def __init__(self, params, tail_params, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
+                 max_grad_norm: float = 0.0):
+        head = [p for p in params if p.requires_grad]
+        tail = [p for p in tail_params if p.requires_grad]
+        if not head or not tail:
+            raise ValueError("FlatAdamSegments needs a non-empty head and a non-empty tail")
+        if any(p is q for p in head for q in tail):
+            raise ValueError("FlatAdamSegments: a parameter is in both segments")
+        super().__init__(head + tail, lr, betas, eps, max_grad_norm)
+        _, self.split = flat_offsets(head)
+        self.head_params, self.tail_params = head, tail
+
+    @property
+    def tail_step(self) -> torch.Tensor:
+        """The tail's step count (a device f32 scalar)."""
+        return self.scalars[OPT_STEP] - self.scalars[OPT_TAIL_SKIPPED]
+
+    def step(self, tail_active: bool = True, grad_scale: float = 1.0):
+        dev = self.params.device
+        call(self.ENTRY, _stream(dev), self.params.data_ptr(), self.grads.data_ptr(),
+             self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.numel, self.split,
+             int(bool(tail_active)), self.lr.data_ptr(), self.betas[0], self.betas[1], self.eps,
+             float(grad_scale), self.max_grad_norm, self.scalars.data_ptr(), self.ws.data_ptr(),
+             self.ws.numel())
