@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCPPO_ABI_VERSION 38
+#define OCPPO_ABI_VERSION 39
 
 /* status codes */
 #define OCPPO_OK 0
@@ -1559,6 +1559,58 @@ OCPPO_API int ocppo_clip_adam_step_seg(ocppo_stream_t stream, float* params, con
                                        double beta2, double eps, double grad_scale,
                                        double max_norm, float* scalars, void* workspace,
                                        size_t workspace_bytes);
+
+/* ---------------------------------------------------------------------------------------------
+ * The recurrent PQN learner (cleanrl/pqn_atari_envpool_lstm.py): where the LSTM and the Q head
+ * meet, ABI 39. All f32, no atomics, no waiting between workgroups, the same result run to run,
+ * graph-capturable. A negative size, a size outside a contract below or a null required pointer
+ * returns OCPPO_E_INVALID before any launch; a zero row / env count launches nothing and returns
+ * OCPPO_OK.
+ *
+ * ocppo_pqn_lstm_act: the rollout step (:261-267) in one launch: ocppo_lstm_step's state update
+ * of every environment (x [N, I], w_ih [4H, I], w_hh [4H, H], b_ih, b_hh [4H], done [N],
+ * h, c [N, H]), then ocppo_pqn_act on the new h (wq [A, H], bq [A], the same seed / step /
+ * step_offset / schedule arguments) inside the workgroup that owns the environment. Both halves
+ * are the device functions of those two entries: h and c are bitwise what ocppo_lstm_step writes,
+ * and actions, values [N], epsilon_out [1] and q_out [N, A] bitwise what ocppo_pqn_act returns on
+ * that h. commit = 1 updates h / c in place; commit = 0 leaves them untouched and writes only
+ * q_out / values (/ actions, epsilon_out when given): the bootstrap of :287, whose state is
+ * dropped. actions may be NULL with commit = 0; epsilon_out and q_out may be NULL.
+ * Contract: H in {32, 64, 128}, 1 <= A <= 18, I >= 1, N >= 1 (N < 2^31), wq 16-byte aligned,
+ * duration > 0. An environment's results do not depend on N or on the other rows.
+ *
+ * ocppo_pqn_head_loss_fwd_bwd: the update's Q head, the MSE loss on the taken action and the
+ * head's backward (:318-325) in one call, one dot product per row (h [M, H], wq [A, H], bq [A],
+ * actions [M] int64, returns [M]):
+ *   q_a[m] = h[m] . wq[a_m] + bq[a_m]
+ *   stats [2] = {mean((returns - q_a)^2), mean(q_a)};   g_m = f32(2 / M) * (q_a[m] - returns[m])
+ *   dh[m] = g_m * wq[a_m]  [M, H]  (f32 products, element by element)
+ *   dwq[a] = sum_{m: a_m = a} g_m * h[m]  [A, H];   dbq[a] = sum_{m: a_m = a} g_m  [A]
+ * Every sum (over H, over the rows, over the workgroups' partials) is accumulated in f64 from exact
+ * f32 x f32 products and rounded to f32 once; g_m above, dh's factor, is f32 arithmetic on the
+ * rounded q_a, while dwq / dbq sum the f64 (2 / M)(q_a - returns) of the unrounded q_a.
+ * dwq / dbq are overwritten; rows of actions nobody took are exact zeros. An action outside [0, A)
+ * is clamped into it, as in ocppo_pqn_loss_fwd_bwd. Two launches of the one call: per-workgroup
+ * partials (a grid that depends on M and H only) go to the workspace with plain stores and are
+ * summed in workgroup order. The workspace (ocppo_pqn_head_loss_workspace_bytes(M, H, A), 16-byte
+ * aligned, no initial contents needed; too small or NULL: OCPPO_E_WORKSPACE) starts with q_a [M],
+ * which the call leaves there for the caller.
+ * Contract: H a multiple of 4 in [4, 1024], 1 <= A <= 18, M >= 1 (M < 2^31); h, wq and dh 16-byte
+ * aligned.
+ * ------------------------------------------------------------------------------------------- */
+OCPPO_API int ocppo_pqn_lstm_act(ocppo_stream_t stream, const float* x, const float* w_ih,
+                                 const float* b_ih, const float* w_hh, const float* b_hh,
+                                 const float* done, int64_t N, int64_t I, int64_t H, float* h,
+                                 float* c, int commit, const float* wq, const float* bq, int64_t A,
+                                 uint64_t seed, const int64_t* step, int64_t step_offset,
+                                 double start_e, double end_e, double duration, int64_t* actions,
+                                 float* values, float* epsilon_out, float* q_out);
+OCPPO_API size_t ocppo_pqn_head_loss_workspace_bytes(int64_t M, int64_t H, int64_t A);
+OCPPO_API int ocppo_pqn_head_loss_fwd_bwd(ocppo_stream_t stream, const float* h, const float* wq,
+                                          const float* bq, const int64_t* actions,
+                                          const float* returns, int64_t M, int64_t H, int64_t A,
+                                          float* dh, float* dwq, float* dbq, float* stats,
+                                          void* workspace, size_t workspace_bytes);
 
 #ifdef __cplusplus
 }

@@ -22,7 +22,7 @@ LIB_PATH = Path(os.environ.get("OCPPO_LIB", PKG / "lib" / "libocppo_hip.so"))
 HEADER = PKG.parent / "include" / "ocppo.h"
 
 # constants mirrored from include/ocppo.h (checked against the header by tests/test_abi.py)
-OCPPO_ABI_VERSION = 38
+OCPPO_ABI_VERSION = 39
 OCPPO_OK, OCPPO_E_INVALID, OCPPO_E_LAUNCH, OCPPO_E_WORKSPACE = 0, 1, 2, 3
 OCPPO_F32, OCPPO_BF16, OCPPO_U8 = 0, 1, 2
 OCPPO_X6_MBITS_ROWS = 2
@@ -182,6 +182,10 @@ SIGNATURES: dict[str, tuple[type, list]] = {
     "ocppo_ppg_aux_loss_fwd_bwd": (I, [P, P, P, P, P, P, I64, I64, D, P, P, P, P, P, SZ]),
     "ocppo_ppg_aux_gather": (I, [P, P, I, P, P, P, I64, I64, I64, I64, I64, P, P, P]),
     "ocppo_clip_adam_step_seg": (I, [P, P, P, P, P, I64, I64, I, P, D, D, D, D, D, P, P, SZ]),
+    "ocppo_pqn_lstm_act": (I, [P, P, P, P, P, P, P, I64, I64, I64, P, P, I, P, P, I64, U64, P, I64,
+                               D, D, D, P, P, P, P]),
+    "ocppo_pqn_head_loss_workspace_bytes": (SZ, [I64, I64, I64]),
+    "ocppo_pqn_head_loss_fwd_bwd": (I, [P, P, P, P, P, P, I64, I64, I64, P, P, P, P, P, SZ]),
 }
 
 

@@ -5,6 +5,7 @@
 // wave64, no atomics: every sum runs in an order fixed by the shapes alone.
 #include "ocppo_common.h"
 #include "ocppo_layernorm.h"
+#include "ocppo_pqn_act.h"
 #include "ocppo_rng.h"
 
 namespace ocppo {
@@ -42,13 +43,7 @@ __global__ __launch_bounds__(256) void q_lambda_kernel(
 }
 
 // ---- Q head + greedy value + epsilon-greedy action ----------------------------------------------
-// One wave per environment: the A <= 18 dot products of the hidden row, each lane over the float4
-// chunks lane, lane + 64, ... of the row and the butterfly over the lanes (every lane ends with
-// every Q value), then the first maximum (torch.argmax's choice on the CPU; a NaN counts as the
-// maximum, as there) and EpsGreedy's coin and random action (ocppo_rng.h: ocppo_epsilon_greedy's).
-constexpr int kPqnMaxA = 18;
-constexpr int kPqnMaxH = 1024;
-
+// One wave per environment runs ocppo_pqn_act.h's pqn_act_row (shared with ocppo_pqn_lstm_act).
 __global__ __launch_bounds__(256) void pqn_act_kernel(
     const float* __restrict__ hidden, int64_t N, int H, const float* __restrict__ wq,
     const float* __restrict__ bq, int A, uint64_t seed, const int64_t* __restrict__ step,
@@ -58,40 +53,8 @@ __global__ __launch_bounds__(256) void pqn_act_kernel(
   const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
   const int64_t n = static_cast<int64_t>(blockIdx.x) * 4 + wv;
   if (n >= N) return;  // wave-uniform
-  constexpr int kCh = kPqnMaxH / 4 / kWave;  // float4 chunks per lane
-  const int H4 = H / 4;
-  float4 x[kCh];
-#pragma unroll
-  for (int c = 0; c < kCh; ++c) {
-    const int i = lane + c * kWave;
-    x[c] = i < H4 ? reinterpret_cast<const float4*>(hidden + n * H)[i]
-                  : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
   const EpsGreedy eg(seed, step[0] + step_offset, start_e, end_e, duration);
-  int best = 0;
-  float bqv = 0.f;
-  for (int j = 0; j < A; ++j) {
-    float acc = 0.f;
-#pragma unroll
-    for (int c = 0; c < kCh; ++c) {
-      const int i = lane + c * kWave;
-      if (i < H4) {
-        const float4 w = reinterpret_cast<const float4*>(wq + static_cast<int64_t>(j) * H)[i];
-        acc += x[c].x * w.x + x[c].y * w.y + x[c].z * w.z + x[c].w * w.w;
-      }
-    }
-    const float q = wave_sum(acc) + bq[j];
-    if (j == 0 || q > bqv || (q != q && bqv == bqv)) {
-      bqv = q;
-      best = j;
-    }
-    if (q_out && lane == 0) q_out[n * A + j] = q;
-  }
-  if (lane == 0) {
-    values[n] = bqv;
-    actions[n] = eg.explore ? eg.random_action(n, A) : static_cast<int64_t>(best);
-    if (eps_out && n == 0) eps_out[0] = static_cast<float>(eg.eps);
-  }
+  pqn_act_row(hidden + n * H, n, H, wq, bq, A, eg, lane, actions, values, eps_out, q_out);
 }
 
 // ---- MSE on the taken action's Q value ----------------------------------------------------------

@@ -142,50 +142,10 @@ def lstm_ok(hidden, done, lstm_state, H: int) -> bool:
     return ops.lstm_shape_ok(hidden.shape[0] // B, B, hidden.shape[1], H)
 
 
-class LSTMAgent(_ActorCritic):
-    """Agent of ppo_atari_lstm.py:117-170 on a trunk of this package: architecture "PPO" is the
-    script's network (NatureCNN + Linear(3136, 512), x / 255 in get_states) with the script's
-    state-dict keys; "PPO_OBJ" is the PPObj encoder / decoder on object vectors."""
-
-    # the torch path's nn.LSTM reaches .grad through AccumulateGrad: the trainer zeroes the flat
-    # gradient buffer per minibatch (PPOTrainer.direct_grads)
-    grads_in_place = False
-
-    def __init__(self, envs, architecture: str = "PPO", lstm_hidden: int = 128, device=None,
-                 encoder_dims=(128, 64), decoder_dims=(128,)):
-        super().__init__()
-        if architecture not in ARCHITECTURES:
-            raise NotImplementedError(architecture)
-        self.device = device
-        self.pixels = architecture == "PPO"
-        dims = tuple(envs.observation_space.shape)
-        if self.pixels:
-            net = nn.Sequential(
-                layer_init(nn.Conv2d(dims[0], 32, 8, stride=4)), nn.ReLU(),
-                layer_init(nn.Conv2d(32, 64, 4, stride=2)), nn.ReLU(),
-                layer_init(nn.Conv2d(64, 64, 3, stride=1)), nn.ReLU(), nn.Flatten())
-            with torch.no_grad():
-                feat = net(torch.zeros((1,) + dims)).shape[1]
-            net.append(layer_init(nn.Linear(feat, 512)))
-            net.append(nn.ReLU())
-            self.network, d = net, 512
-        else:
-            layers, d = object_trunk(dims, tuple(encoder_dims), tuple(decoder_dims), layer_init)
-            self.network = nn.Sequential(*layers)
-        self.lstm = nn.LSTM(d, lstm_hidden)
-        for name, param in self.lstm.named_parameters():  # :132-136
-            if "bias" in name:
-                nn.init.constant_(param, 0)
-            elif "weight" in name:
-                nn.init.orthogonal_(param, 1.0)
-        self.actor = layer_init(nn.Linear(lstm_hidden, envs.action_space.n), std=0.01)
-        self.critic = layer_init(nn.Linear(lstm_hidden, 1), std=1)
-
-    def trunk(self, x, prescaled: bool = False):
-        """The LSTM's input [rows, trunk_out] (:141); pixels are divided by 255 here."""
-        if self.pixels and not prescaled:
-            x = x / 255.0
-        return fused_trunk(self.network, x)
+class Recurrence:
+    """The masked single-layer recurrence (:144-158) of a module that holds `self.lstm`, an
+    nn.LSTM: the fused kernels under lstm_ok, else the reference's per-step torch loop. Shared by
+    LSTMAgent and the recurrent PQN network (pqn_lstm.PQNLSTMNetwork)."""
 
     @property
     def _ih(self):
@@ -228,6 +188,57 @@ class LSTMAgent(_ActorCritic):
 
     def get_states(self, x, lstm_state, done):
         return self.recur(self.trunk(x), lstm_state, done)
+
+
+def init_lstm(lstm: nn.LSTM) -> nn.LSTM:
+    """:132-136: zero biases, orthogonal (gain 1) weights, in named_parameters' order."""
+    for name, param in lstm.named_parameters():
+        if "bias" in name:
+            nn.init.constant_(param, 0)
+        elif "weight" in name:
+            nn.init.orthogonal_(param, 1.0)
+    return lstm
+
+
+class LSTMAgent(_ActorCritic, Recurrence):
+    """Agent of ppo_atari_lstm.py:117-170 on a trunk of this package: architecture "PPO" is the
+    script's network (NatureCNN + Linear(3136, 512), x / 255 in get_states) with the script's
+    state-dict keys; "PPO_OBJ" is the PPObj encoder / decoder on object vectors."""
+
+    # the torch path's nn.LSTM reaches .grad through AccumulateGrad: the trainer zeroes the flat
+    # gradient buffer per minibatch (PPOTrainer.direct_grads)
+    grads_in_place = False
+
+    def __init__(self, envs, architecture: str = "PPO", lstm_hidden: int = 128, device=None,
+                 encoder_dims=(128, 64), decoder_dims=(128,)):
+        super().__init__()
+        if architecture not in ARCHITECTURES:
+            raise NotImplementedError(architecture)
+        self.device = device
+        self.pixels = architecture == "PPO"
+        dims = tuple(envs.observation_space.shape)
+        if self.pixels:
+            net = nn.Sequential(
+                layer_init(nn.Conv2d(dims[0], 32, 8, stride=4)), nn.ReLU(),
+                layer_init(nn.Conv2d(32, 64, 4, stride=2)), nn.ReLU(),
+                layer_init(nn.Conv2d(64, 64, 3, stride=1)), nn.ReLU(), nn.Flatten())
+            with torch.no_grad():
+                feat = net(torch.zeros((1,) + dims)).shape[1]
+            net.append(layer_init(nn.Linear(feat, 512)))
+            net.append(nn.ReLU())
+            self.network, d = net, 512
+        else:
+            layers, d = object_trunk(dims, tuple(encoder_dims), tuple(decoder_dims), layer_init)
+            self.network = nn.Sequential(*layers)
+        self.lstm = init_lstm(nn.LSTM(d, lstm_hidden))
+        self.actor = layer_init(nn.Linear(lstm_hidden, envs.action_space.n), std=0.01)
+        self.critic = layer_init(nn.Linear(lstm_hidden, 1), std=1)
+
+    def trunk(self, x, prescaled: bool = False):
+        """The LSTM's input [rows, trunk_out] (:141); pixels are divided by 255 here."""
+        if self.pixels and not prescaled:
+            x = x / 255.0
+        return fused_trunk(self.network, x)
 
     def get_value(self, x, lstm_state, done):
         hidden, _ = self.get_states(x, lstm_state, done)

@@ -3301,6 +3301,114 @@ class FlatRAdam(FlatAdam):
 
 
 # ---------------------------------------------------------------------------------------------
+# Recurrent PQN (pqn_atari_envpool_lstm.py): the LSTM step + acting step in one launch, and the
+# update's Q head + MSE loss + head backward in one call (csrc/ocppo_pqn_lstm.hip)
+# ---------------------------------------------------------------------------------------------
+def pqn_lstm_act_ok(x, h, wq) -> bool:
+    """pqn_lstm_act applies: GPU f32 contiguous x [N, I], h [N, H] with (N, I, H) inside
+    lstm_shape_ok, and a contiguous 16-B aligned head wq [A, H] with 1 <= A <= 18."""
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and
+               t.dim() == 2 and t.is_contiguous() for t in (x, h, wq)):
+        return False
+    (N, I), H, A = x.shape, h.shape[1], wq.shape[0]
+    return (h.shape[0] == N and wq.shape[1] == H and lstm_shape_ok(1, N, I, H) and
+            1 <= A <= PQN_MAX_ACTIONS and wq.data_ptr() % 16 == 0)
+
+
+def pqn_lstm_act(x, w_ih, b_ih, w_hh, b_hh, done, h, c, wq, bq, seed: int, step, start_e: float,
+                 end_e: float, duration: float, actions_out=None, values_out=None,
+                 epsilon_out=None, step_offset: int = 0, q_out=None, commit: bool = True):
+    """The rollout step of pqn_atari_envpool_lstm.py:261-267 in one launch: lstm_step on (x, done,
+    h, c), then pqn_act on the new h -- bitwise those two calls. commit=True updates h / c in
+    place and returns (actions, values); commit=False leaves h / c untouched (the bootstrap of
+    :287): no action is drawn (actions_out is not written unless given), returns (None or
+    actions_out, values)."""
+    if not pqn_lstm_act_ok(x, h, wq):
+        raise ValueError(f"pqn_lstm_act: x {tuple(getattr(x, 'shape', ()))}, h "
+                         f"{tuple(getattr(h, 'shape', ()))}, wq {tuple(getattr(wq, 'shape', ()))} "
+                         f"outside pqn_lstm_act_ok")
+    (N, I), H, A = x.shape, h.shape[1], wq.shape[0]
+    dev, f = x.device, torch.float32
+    if actions_out is None and commit:
+        actions_out = torch.empty(N, dtype=torch.int64, device=dev)
+    if values_out is None:
+        values_out = torch.empty(N, dtype=f, device=dev)
+    call("ocppo_pqn_lstm_act", _stream(dev), x.data_ptr(), _check(w_ih, "w_ih", f, dev, 4 * H * I),
+         _check(b_ih, "b_ih", f, dev, 4 * H), _check(w_hh, "w_hh", f, dev, 4 * H * H),
+         _check(b_hh, "b_hh", f, dev, 4 * H), _check(done, "done", f, dev, N), N, I, H,
+         h.data_ptr(), _check(c, "c", f, dev, N * H), int(bool(commit)), wq.data_ptr(),
+         _check(bq, "bq", f, dev, A), A, int(seed) & 0xFFFFFFFFFFFFFFFF,
+         _check(step, "step", torch.int64, dev, 1), int(step_offset), float(start_e), float(end_e),
+         float(duration), _opt(actions_out, "actions", torch.int64, dev, N),
+         _check(values_out, "values", f, dev, N), _opt(epsilon_out, "epsilon_out", f, dev, 1),
+         _opt(q_out, "q_out", f, dev, N * A))
+    return actions_out, values_out
+
+
+PQN_HEAD_LOSS_MAX_H = 1024
+
+
+def pqn_head_loss_ok(h, wq) -> bool:
+    """pqn_head_loss_fwd_bwd applies: GPU f32 contiguous 16-B aligned h [M >= 1, H] and wq [A, H]
+    with H a multiple of 4 in [4, 1024] and 1 <= A <= 18."""
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and
+               t.dim() == 2 and t.is_contiguous() and t.data_ptr() % 16 == 0 for t in (h, wq)):
+        return False
+    (M, H), A = h.shape, wq.shape[0]
+    return (wq.shape[1] == H and M >= 1 and 4 <= H <= PQN_HEAD_LOSS_MAX_H and H % 4 == 0 and
+            1 <= A <= PQN_MAX_ACTIONS)
+
+
+class HeadLossWorkspace:
+    """Device scratch of pqn_head_loss_fwd_bwd for one (M, H, A): the per-workgroup partials (no
+    initial contents needed) behind the rows' q_a, which every call leaves in `q_taken`."""
+
+    def __init__(self, M: int, H: int, A: int, device):
+        self.nbytes = int(_lib.LIB.ocppo_pqn_head_loss_workspace_bytes(M, H, A))
+        if self.nbytes == 0:
+            raise ValueError(f"HeadLossWorkspace: M={M} H={H} A={A} outside the contract")
+        self.buf = torch.zeros(self.nbytes // 4, dtype=torch.float32, device=device)
+        self.M, self.H, self.A = M, H, A
+
+    @property
+    def q_taken(self):
+        """q_a [M] of the last call: h[m] . wq[a_m] + bq[a_m]."""
+        return self.buf[:self.M]
+
+
+def pqn_head_loss_fwd_bwd(h, wq, bq, actions, returns, dh=None, dwq=None, dbq=None, stats=None,
+                          workspace: HeadLossWorkspace | None = None):
+    """The update's Q head, F.mse_loss(returns, q.gather(1, actions)) and the head's backward of
+    pqn_atari_envpool_lstm.py:318-325 in one call, from the head's input h [M, H]:
+    (stats [2] = {td_loss, mean q(s, a)}, dh [M, H], dwq [A, H], dbq [A]); dwq / dbq are
+    overwritten (point them at the head's .grad views)."""
+    if not pqn_head_loss_ok(h, wq):
+        raise ValueError(f"pqn_head_loss_fwd_bwd: h {tuple(getattr(h, 'shape', ()))}, wq "
+                         f"{tuple(getattr(wq, 'shape', ()))} outside pqn_head_loss_ok")
+    (M, H), A = h.shape, wq.shape[0]
+    dev, f = h.device, torch.float32
+    if dh is None:
+        dh = torch.empty_like(h)
+    if dwq is None:
+        dwq = torch.empty_like(wq)
+    if dbq is None:
+        dbq = torch.empty(A, dtype=f, device=dev)
+    if stats is None:
+        stats = torch.empty(2, dtype=f, device=dev)
+    if workspace is None:
+        workspace = HeadLossWorkspace(M, H, A, dev)
+    if (workspace.M, workspace.H, workspace.A) != (M, H, A) or workspace.buf.device != dev:
+        raise ValueError(f"pqn_head_loss_fwd_bwd: workspace of {(workspace.M, workspace.H, workspace.A)}"
+                         f" for M, H, A = {(M, H, A)}")
+    call("ocppo_pqn_head_loss_fwd_bwd", _stream(dev), h.data_ptr(), wq.data_ptr(),
+         _check(bq, "bq", f, dev, A), _check(actions, "actions", torch.int64, dev, M),
+         _check(returns, "returns", f, dev, M), M, H, A, _check(dh, "dh", f, dev, M * H),
+         _check(dwq, "dwq", f, dev, A * H), _check(dbq, "dbq", f, dev, A),
+         _check(stats, "stats", f, dev, 2), workspace.buf.data_ptr(), workspace.nbytes)
+    return stats, dh, dwq, dbq
+
+
+# ---------------------------------------------------------------------------------------------
 # Discrete SAC (sac_atari.py): acting, twin soft-Q loss, policy + temperature loss and its Adam
 # ---------------------------------------------------------------------------------------------
 SAC_MAX_ACTIONS = C51_MAX_ACTIONS

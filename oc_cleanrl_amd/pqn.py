@@ -147,6 +147,57 @@ def _fusable_norm(x, ln) -> bool:
             (FUSED_LN_UPDATE or not torch.is_grad_enabled()))
 
 
+def trunk_layers(envs, pixels: bool, encoder_dims=(128, 64), decoder_dims=(128,)):
+    """(modules, output width) of the network below the Q head, made in the script's order
+    (:119-134): the pixel stack, or the PPObj encoder / decoder (agents.object_trunk) with a
+    LayerNorm(width) between every Linear and its ReLU. Shared with the recurrent PQN network."""
+    dims = tuple(envs.observation_space.shape)
+    if pixels:
+        convs = [(32, 8, 4), (64, 4, 2), (64, 3, 1)]
+        layers, c, hw = [], dims[0], dims[1]
+        for cout, k, s in convs:
+            hw = (hw - k) // s + 1
+            layers += [layer_init(nn.Conv2d(c, cout, k, stride=s)),
+                       nn.LayerNorm([cout, hw, hw]), nn.ReLU()]
+            c = cout
+        layers += [nn.Flatten(), layer_init(nn.Linear(c * hw * hw, 512)), nn.LayerNorm(512),
+                   nn.ReLU()]
+        return layers, 512
+    plain, d = object_trunk(dims, tuple(encoder_dims), tuple(decoder_dims), layer_init)
+    layers = []
+    for m in plain:  # LayerNorm draws nothing: the seeded init is object_trunk's
+        layers.append(m)
+        if isinstance(m, nn.Linear):
+            layers.append(nn.LayerNorm(m.out_features))
+    return layers, d
+
+
+def run_trunk(mods, x):
+    """The modules below the Q head on x: a fusable Linear is agents.linear_act, a fusable
+    LayerNorm [-> ReLU] one ops.ln_relu launch, anything else the module itself."""
+    i = 0
+    while i < len(mods):
+        m = mods[i]
+        if _fusable_linear(x, m):
+            x = linear_act(x, m, False)
+        elif _fusable_norm(x, m):
+            relu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
+            x = ops.timed("ln_relu", lambda h=x, ln=m, relu=relu: ops.ln_relu(
+                h, ln.weight, ln.bias, ln.eps, relu))
+            i += 1 if relu else 0
+        else:
+            x = m(x)
+        i += 1
+    return x
+
+
+def q_head(lin, hidden):
+    """Q values [rows, A] of the head `lin` on its input rows."""
+    if FUSED_PQN and hidden.is_cuda and hidden.dtype == torch.float32:
+        return linear_act(hidden, lin, False)
+    return lin(hidden)
+
+
 class PQNetwork(Predictor):
     """QNetwork of pqn_atari_envpool.py:117-138. architecture "PQN": the script's pixel network
     with its state-dict keys (network.0 .. network.13) and seeded init; "PQN_OBJ": the PPObj
@@ -165,26 +216,8 @@ class PQNetwork(Predictor):
             raise NotImplementedError(architecture)
         self.device = device
         self.pixels = architecture == "PQN"
-        dims = tuple(envs.observation_space.shape)
-        A = envs.action_space.n
-        if self.pixels:
-            convs = [(32, 8, 4), (64, 4, 2), (64, 3, 1)]
-            layers, c, hw = [], dims[0], dims[1]
-            for cout, k, s in convs:
-                hw = (hw - k) // s + 1
-                layers += [layer_init(nn.Conv2d(c, cout, k, stride=s)),
-                           nn.LayerNorm([cout, hw, hw]), nn.ReLU()]
-                c = cout
-            layers += [nn.Flatten(), layer_init(nn.Linear(c * hw * hw, 512)), nn.LayerNorm(512),
-                       nn.ReLU(), layer_init(nn.Linear(512, A))]
-        else:
-            plain, d = object_trunk(dims, tuple(encoder_dims), tuple(decoder_dims), layer_init)
-            layers = []
-            for m in plain:  # LayerNorm draws nothing: the seeded init is object_trunk's
-                layers.append(m)
-                if isinstance(m, nn.Linear):
-                    layers.append(nn.LayerNorm(m.out_features))
-            layers.append(layer_init(nn.Linear(d, A)))
+        layers, d = trunk_layers(envs, self.pixels, encoder_dims, decoder_dims)
+        layers.append(layer_init(nn.Linear(d, envs.action_space.n)))
         self.network = nn.Sequential(*layers)
 
     @property
@@ -195,28 +228,11 @@ class PQNetwork(Predictor):
         """The Q head's input [rows, d] (pixels are divided by 255 here, :138)."""
         if self.pixels and not prescaled:
             x = x / 255.0
-        mods = list(self.network)[:-1]
-        i = 0
-        while i < len(mods):
-            m = mods[i]
-            if _fusable_linear(x, m):
-                x = linear_act(x, m, False)
-            elif _fusable_norm(x, m):
-                relu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
-                x = ops.timed("ln_relu", lambda h=x, ln=m, relu=relu: ops.ln_relu(
-                    h, ln.weight, ln.bias, ln.eps, relu))
-                i += 1 if relu else 0
-            else:
-                x = m(x)
-            i += 1
-        return x
+        return run_trunk(list(self.network)[:-1], x)
 
     def q_head(self, hidden):
         """Q values [rows, A] of the trunk output."""
-        lin = self.q_lin
-        if FUSED_PQN and hidden.is_cuda and hidden.dtype == torch.float32:
-            return linear_act(hidden, lin, False)
-        return lin(hidden)
+        return q_head(self.q_lin, hidden)
 
     def forward(self, x):
         return self.q_head(self.trunk(x))
