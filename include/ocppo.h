@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCPPO_ABI_VERSION 39
+#define OCPPO_ABI_VERSION 40
 
 /* status codes */
 #define OCPPO_OK 0
@@ -1611,6 +1611,51 @@ OCPPO_API int ocppo_pqn_head_loss_fwd_bwd(ocppo_stream_t stream, const float* h,
                                           const float* returns, int64_t M, int64_t H, int64_t A,
                                           float* dh, float* dwq, float* dbq, float* stats,
                                           void* workspace, size_t workspace_bytes);
+
+/* ---------------------------------------------------------------------------------------------
+ * The QDagger learner (cleanrl/qdagger_dqn_atari_impalacnn.py) on the DQN loop, ABI 40. All f32,
+ * one workgroup each, no atomics, sums in a fixed order (wave shuffles and LDS): the same result
+ * run to run; graph-capturable. Bad sizes and null required pointers return OCPPO_E_INVALID
+ * before any launch.
+ *
+ * ocppo_qdagger_loss_fwd_bwd: the loss of :303-315 / :412-424 and d loss / d q in one launch.
+ * q, q_next, q_teacher [B, A] (student(obs), target(next_obs), teacher(obs)), actions [B] int64,
+ * rewards, dones [B]; T = temperature, c = *distill_coeff (NULL: 1.0, the offline phase):
+ *   y_b     = r_b + (f32(gamma) * max_a q_next[b, a]) * (1 - d_b)
+ *   q_loss  = mean_b (y_b - q[b, a_b])^2
+ *   t = q_teacher / T,  s = q / T
+ *   distill = sum_b sum_a -softmax(t)[b, a] * (log_softmax(s)[b, a] - log_softmax(t)[b, a])
+ *   loss    = q_loss + c * distill
+ *   dq[b, a] = f32(2 / B) (q[b, a_b] - y_b) [a == a_b]
+ *              + ((softmax(s)[b, a] * sum_a' softmax(t)[b, a'] - softmax(t)[b, a]) * c) / T
+ * distill is a SUM over the batch, as in the script: its kl_divergence_with_logits returns a
+ * scalar, so the torch.mean around it does nothing. The teacher's softmax sum in dq is taken as
+ * (sum_a' e_a') / Z = 1, so a student row equal to the teacher's has a zero distillation gradient
+ * and dq is then the TD gradient's bits. The TD half is ocppo_td_loss_fwd_bwd's device code: with
+ * c = 0, dq, stats[1] and stats[3] are bitwise that call's dq, stats[0] and stats[1].
+ *   stats [5] = {loss, q_loss, distill, mean_b q[b, a_b], c}
+ * Contract: B >= 1, 1 <= A <= 1024, temperature > 0.
+ *
+ * ocppo_qdagger_episode_push: the deque(maxlen=10) of episodic returns (:365, :390) and the
+ * coefficient of :408-411, once per env step, from the env's raw reward [E] and done [E] (f32,
+ * done != 0 ends an episode). Envs are visited in ascending index order:
+ *   run_ret[e] += reward[e] (f32);  on done: ring[head] = run_ret[e], head = (head + 1) % 10,
+ *   count = min(count + 1, 10), run_ret[e] = 0
+ *   coeff_out[0] = count < 10 ? 1 : f32(max(1 - mean(ring) / teacher_mean, 0))
+ * with the mean summed in f64 from the oldest return to the newest. run_ret [E] f32, ring [10]
+ * f32, ring_state [2] int64 = {head, count} (all zero at the start).
+ * Contract: E >= 1, teacher_mean finite and not 0.
+ * ------------------------------------------------------------------------------------------- */
+OCPPO_API int ocppo_qdagger_loss_fwd_bwd(ocppo_stream_t stream, const float* q,
+                                         const float* q_next, const float* q_teacher,
+                                         const int64_t* actions, const float* rewards,
+                                         const float* dones, int64_t B, int64_t A, double gamma,
+                                         double temperature, const float* distill_coeff,
+                                         float* dq, float* stats);
+OCPPO_API int ocppo_qdagger_episode_push(ocppo_stream_t stream, const float* reward,
+                                         const float* done, int64_t E, float* run_ret,
+                                         float* ring, int64_t* ring_state, double teacher_mean,
+                                         float* coeff_out);
 
 #ifdef __cplusplus
 }

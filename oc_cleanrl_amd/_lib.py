@@ -22,7 +22,7 @@ LIB_PATH = Path(os.environ.get("OCPPO_LIB", PKG / "lib" / "libocppo_hip.so"))
 HEADER = PKG.parent / "include" / "ocppo.h"
 
 # constants mirrored from include/ocppo.h (checked against the header by tests/test_abi.py)
-OCPPO_ABI_VERSION = 39
+OCPPO_ABI_VERSION = 40
 OCPPO_OK, OCPPO_E_INVALID, OCPPO_E_LAUNCH, OCPPO_E_WORKSPACE = 0, 1, 2, 3
 OCPPO_F32, OCPPO_BF16, OCPPO_U8 = 0, 1, 2
 OCPPO_X6_MBITS_ROWS = 2
@@ -186,6 +186,8 @@ SIGNATURES: dict[str, tuple[type, list]] = {
                                D, D, D, P, P, P, P]),
     "ocppo_pqn_head_loss_workspace_bytes": (SZ, [I64, I64, I64]),
     "ocppo_pqn_head_loss_fwd_bwd": (I, [P, P, P, P, P, P, I64, I64, I64, P, P, P, P, P, SZ]),
+    "ocppo_qdagger_loss_fwd_bwd": (I, [P, P, P, P, P, P, P, I64, I64, D, D, P, P, P]),
+    "ocppo_qdagger_episode_push": (I, [P, P, P, I64, P, P, P, D, P]),
 }
 
 

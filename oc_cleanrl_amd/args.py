@@ -190,7 +190,7 @@ def parse_dataclass(cls, argv=None, defaults: dict | None = None, description: s
         elif isinstance(cur, tuple):
             tuples.append(f.name)
             ap.add_argument(*names, dest=f.name, nargs="*", type=int, default=cur)
-        elif f.name in ("target_kl",):
+        elif f.name in ("target_kl", "teacher_return"):  # Optional[float]
             ap.add_argument(*names, dest=f.name, type=lambda s: None if s == "None" else float(s),
                             default=cur)
         elif cur is None:

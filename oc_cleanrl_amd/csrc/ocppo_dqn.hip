@@ -15,6 +15,7 @@
 #include "ocppo_rng.h"
 #include "ocppo_store.h"
 #include "ocppo_synth_env.h"
+#include "ocppo_td.h"
 
 namespace ocppo {
 
@@ -193,7 +194,8 @@ __global__ __launch_bounds__(256) void q_head_eps_kernel(
 // Fused TD target + MSE loss, forward and backward w.r.t. q (dqn_atari_oc.py:378-382):
 //   target_max = max_a q_next;  td = r + (f32(gamma) * target_max) * (1 - d)
 //   old = q[b, a_b];  loss = mean((td - old)^2);  dq[b, j] = j == a_b ? (old - td) * (2/B) : 0
-// One workgroup (B is the DQN minibatch, 32 in the reference).
+// One workgroup (B is the DQN minibatch, 32 in the reference). The row code and the reduction are
+// ocppo_td.h's, shared with the QDagger loss.
 __global__ __launch_bounds__(1024) void td_loss_kernel(const float* __restrict__ q,
                                                        const float* __restrict__ q_next,
                                                        const int64_t* __restrict__ actions,
@@ -205,22 +207,15 @@ __global__ __launch_bounds__(1024) void td_loss_kernel(const float* __restrict__
   __shared__ float scratch[16];
   float se = 0.f, sq = 0.f;
   for (int64_t b = threadIdx.x; b < B; b += blockDim.x) {
-    float m = q_next[b * A];
-    for (int j = 1; j < A; ++j) m = fmaxf(m, q_next[b * A + j]);
-    const float td = rewards[b] + (gamma * m) * (1.0f - dones[b]);
-    const int64_t a = actions[b];
-    const float old = q[b * A + a];
-    const float diff = td - old;
-    se += diff * diff;
-    sq += old;
-    const float g = (old - td) * norm;  // mse_loss_backward w.r.t. its `target` argument
+    int64_t a;
+    const float g = td_row(q, q_next, actions, rewards, dones, b, A, gamma, norm, a, se, sq);
     for (int j = 0; j < A; ++j) dq[b * A + j] = j == a ? g : 0.f;
   }
-  se = block_sum(se, scratch);
-  sq = block_sum(sq, scratch);
+  float td_loss, q_mean;
+  td_reduce(se, sq, B, scratch, td_loss, q_mean);
   if (threadIdx.x == 0) {
-    stats[0] = se / static_cast<float>(B);  // losses/td_loss
-    stats[1] = sq / static_cast<float>(B);  // losses/q_values (old_val.mean())
+    stats[0] = td_loss;
+    stats[1] = q_mean;
   }
 }
 
@@ -510,10 +505,8 @@ extern "C" int ocppo_td_loss_fwd_bwd(ocppo_stream_t stream, const float* q, cons
   OCPPO_REQUIRE(q && q_next && actions && rewards && dones && dq && stats,
                 "ocppo_td_loss_fwd_bwd: null pointer");
   clear_stale_error();
-  // mse_loss backward: norm = 2 / numel (computed in double by ATen, applied in f32)
-  const float norm = static_cast<float>(2.0 / static_cast<double>(B));
   hipLaunchKernelGGL(td_loss_kernel, dim3(1), dim3(256), 0, as_stream(stream), q, q_next, actions,
-                     rewards, dones, B, (int)A, static_cast<float>(gamma), norm, dq, stats);
+                     rewards, dones, B, (int)A, static_cast<float>(gamma), td_norm(B), dq, stats);
   return check_launch("ocppo_td_loss_fwd_bwd");
 }
 

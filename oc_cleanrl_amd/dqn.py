@@ -246,9 +246,13 @@ class DQNTrainer:
         """Every layer of self.q writes its gradients in place (no zero_grad before backward)."""
         return all(isinstance(m, (nn.Linear, nn.ReLU, nn.Flatten)) for m in self.q.network)
 
+    def _actor(self) -> nn.Module:
+        """The network that acts in _env_step (QDagger: the teacher while it fills its replay)."""
+        return self.q
+
     def _fused_act_ok(self) -> bool:
         """Acting as the Q head and the epsilon-greedy choice in one launch."""
-        head = self.q.network[-1]
+        head = self._actor().network[-1]
         return (FUSED_ACT and isinstance(head, nn.Linear) and head.bias is not None and
                 self.A <= 8 and head.in_features % 256 == 0 and head.in_features <= 1024)
 
@@ -261,7 +265,7 @@ class DQNTrainer:
     def _act(self, k: int):
         """Greedy / random actions of global step chunk base + k + 1 from the whole network."""
         a = self.args
-        q = self.q.q_values(self.net_obs)
+        q = self._actor().q_values(self.net_obs)
         ops.epsilon_greedy(q, a.seed, self.step_dev, a.start_e, a.end_e, self.duration,
                            self.actions, self.epsilon, step_offset=k + 1)
 
@@ -274,7 +278,7 @@ class DQNTrainer:
         # global step = chunk base (step_dev, advanced once per chunk) + k + 1
         with torch.no_grad():
             if self.fused_act:
-                net = self.q.network
+                net = self._actor().network
                 x = self.net_obs / 255.0 if self.pixels else self.net_obs
                 h = fused_trunk(net[:-1], x)
                 if FUSED_ACT_STEP and not self.pixels and ops.dqn_act_step_ok(

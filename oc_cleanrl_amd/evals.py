@@ -13,6 +13,8 @@ is the env kernel's RecordEpisodeStatistics counters, read once per step (the re
 """
 from __future__ import annotations
 
+import random
+
 import torch
 
 from . import ops
@@ -57,21 +59,28 @@ class EvalEnv:
 
 
 def make_env(idx: int = 0, env_id: str = "ALE/Pong-v5", obs_mode: str = "obj",
-             num_features: int = 12, seed: int = 0, device="cuda", **_):
+             num_features: int = 12, seed: int = 0, device="cuda", window: int = 4, **_):
     """The reference's `make_env(idx=0, **env_kwargs)` factory shape (capture_video, run_dir
     and other gym-only kwargs are accepted and ignored)."""
-    return EvalEnv(env_id, obs_mode, num_features, seed + idx, device)
+    return EvalEnv(env_id, obs_mode, num_features, seed + idx, device, window)
 
 
-def evaluate(agent, make_env, eval_episodes: int, device, **env_kwargs):
-    """generic_eval.py:7-29 semantics: episodic returns of `eval_episodes` finished episodes."""
+def evaluate(agent, make_env, eval_episodes: int, device, epsilon: float = 0.0,
+             epsilon_seed: int = 0, **env_kwargs):
+    """generic_eval.py:7-29 semantics: episodic returns of `eval_episodes` finished episodes.
+    epsilon > 0 (dqn_eval.py's argument): with that probability a step takes a uniform random
+    action, drawn from a host generator seeded with `epsilon_seed`."""
     env = make_env(idx=0, device=device, **env_kwargs)
     agent.eval()
     obs = env.reset()
     episodic_returns: list = []
+    rng = random.Random(epsilon_seed) if epsilon > 0 else None
     with torch.no_grad():
         while len(episodic_returns) < eval_episodes:
-            actions = agent.get_action_and_value(obs)[0]
+            if rng is not None and rng.random() < epsilon:
+                actions = torch.tensor([rng.randrange(env.n_actions)], device=obs.device)
+            else:
+                actions = agent.get_action_and_value(obs)[0]
             obs, finished = env.step(actions)
             episodic_returns += finished
     return episodic_returns[:eval_episodes] if len(episodic_returns) > eval_episodes \

@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import ctypes
 import functools
+import math
 
 import torch
 
@@ -3814,3 +3815,72 @@ class FlatAdamSegments(FlatAdam):
              int(bool(tail_active)), self.lr.data_ptr(), self.betas[0], self.betas[1], self.eps,
              float(grad_scale), self.max_grad_norm, self.scalars.data_ptr(), self.ws.data_ptr(),
              self.ws.numel())
+
+
+# ---------------------------------------------------------------------------------------------
+# QDagger (qdagger_dqn_atari_impalacnn.py): the TD + distillation loss, the episodic-return ring
+# ---------------------------------------------------------------------------------------------
+QDAGGER_RING = 10  # the script's deque(maxlen=10)
+
+
+def qdagger_loss_fwd_bwd(q, q_next, q_teacher, actions, rewards, dones, gamma: float,
+                         temperature: float, distill_coeff=None, dq=None, stats=None):
+    """:303-315 / :412-424 in one launch. distill_coeff: a device f32 scalar, None = 1.0 (the
+    offline phase). Returns (stats [5] = {loss, q_loss, distill_loss, mean q(s,a), coeff}, dq)."""
+    if not isinstance(q, torch.Tensor) or q.dim() != 2:
+        raise ValueError("qdagger_loss_fwd_bwd: q: expected a [B, A] tensor")
+    B, A = q.shape
+    if not (B >= 1 and 1 <= A <= 1024):
+        raise ValueError(f"qdagger_loss_fwd_bwd: B={B} A={A}: need B >= 1 and 1 <= A <= 1024")
+    if not temperature > 0:
+        raise ValueError(f"qdagger_loss_fwd_bwd: temperature={temperature} must be > 0")
+    dev = q.device
+    f = torch.float32
+    if dq is None:
+        dq = torch.empty_like(q)
+    if stats is None:
+        stats = torch.empty(5, dtype=f, device=dev)
+    call("ocppo_qdagger_loss_fwd_bwd", _stream(dev), _check(q, "q", f, dev),
+         _check(q_next, "q_next", f, dev, B * A), _check(q_teacher, "q_teacher", f, dev, B * A),
+         _check(actions, "actions", torch.int64, dev, B), _check(rewards, "rewards", f, dev, B),
+         _check(dones, "dones", f, dev, B), B, A, float(gamma), float(temperature),
+         _opt(distill_coeff, "distill_coeff", f, dev, 1), _check(dq, "dq", f, dev, B * A),
+         _check(stats, "stats", f, dev, 5))
+    return stats, dq
+
+
+class EpisodeRing:
+    """The device state of qdagger_episode_push: the envs' running returns, the 10-slot ring of
+    finished returns with its int64 {head, count}, and the coefficient the loss launch reads."""
+
+    def __init__(self, num_envs: int, device):
+        dev, f = torch.device(device), torch.float32
+        self.run_ret = torch.zeros(num_envs, dtype=f, device=dev)
+        self.ring = torch.zeros(QDAGGER_RING, dtype=f, device=dev)
+        self.state = torch.zeros(2, dtype=torch.int64, device=dev)
+        self.coeff = torch.ones(1, dtype=f, device=dev)
+
+    def returns(self) -> list:
+        """The ring's returns, oldest first (one host sync)."""
+        head, count = self.state.tolist()
+        r = self.ring.tolist()
+        return r[:count] if count < QDAGGER_RING else r[head:] + r[:head]
+
+
+def qdagger_episode_push(reward, done, ring: EpisodeRing, teacher_mean: float):
+    """:365, :390 and :408-411 for one env step: the raw reward [E] and done [E] go into the
+    running returns, finished episodes into the ring in ascending env order, and ring.coeff
+    becomes 1 below 10 episodes, else max(1 - mean(ring) / teacher_mean, 0)."""
+    dev = reward.device
+    f = torch.float32
+    E = reward.numel()
+    teacher_mean = float(teacher_mean)
+    if teacher_mean == 0 or not math.isfinite(teacher_mean):
+        raise ValueError(f"qdagger_episode_push: teacher_mean={teacher_mean} must be finite and "
+                         "not 0")
+    call("ocppo_qdagger_episode_push", _stream(dev), _check(reward, "reward", f, dev),
+         _check(done, "done", f, dev, E), E, _check(ring.run_ret, "run_ret", f, dev, E),
+         _check(ring.ring, "ring", f, dev, QDAGGER_RING),
+         _check(ring.state, "ring_state", torch.int64, dev, 2), teacher_mean,
+         _check(ring.coeff, "coeff_out", f, dev, 1))
+    return ring.coeff
