@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCPPO_ABI_VERSION 40
+#define OCPPO_ABI_VERSION 41
 
 /* status codes */
 #define OCPPO_OK 0
@@ -1656,6 +1656,61 @@ OCPPO_API int ocppo_qdagger_episode_push(ocppo_stream_t stream, const float* rew
                                          const float* done, int64_t E, float* run_ret,
                                          float* ring, int64_t* ring_state, double teacher_mean,
                                          float* coeff_out);
+
+/* ---------------------------------------------------------------------------------------------
+ * Continuous-action PPO / RPO (cleanrl/ppo_continuous_action.py, rpo_continuous_action.py): a
+ * diagonal-Gaussian policy of A <= 64 action dimensions. f32 unless stated, no atomics (every
+ * cross-row sum is two fixed-order stages), graph-capturable.
+ *
+ * ocppo_gauss_head_sample (:134-141): mean, z [N, A], logstd [A], value_in [N] ->
+ *   action = z * exp(logstd) + mean (two roundings, as torch.normal), logprob [N] = the row sum of
+ *   Normal.log_prob in column order, value = value_in.
+ * ocppo_gauss_ppo_loss_fwd_bwd (:265-300 from the network outputs on, with the backward, one
+ *   launch): mean [M, A], logstd [A], new_value [M], the minibatch's actions [M, A], old
+ *   log-probs, advantages, returns, old values [M], adv_stats [2] (mean, unbiased std; norm_adv)
+ *   -> dmean [M, A], dvalue [M], dlogstd [A] (summed over rows, the entropy bonus included), stats
+ *   [OCPPO_NUM_STATS]. Ties of both max() as ocppo_ppo_loss_fwd_bwd. rpo_alpha > 0: mean[m, a] +=
+ *   u in [-alpha, alpha) from the library's Philox stream keyed by (seed, rpo_counter[0], mb, m,
+ *   a), rpo_counter a device int64 the caller advances; rpo_alpha == 0 is bitwise the launch
+ *   without it. ocppo_rpo_noise writes the same draws [M, A].
+ * ocppo_env_normalize (:96-100: NormalizeObservation, clip +-10, NormalizeReward(gamma), clip
+ *   +-10) on N envs' raw step outputs, per-env statistics norm_state [N, 2D + 5] f64 = {obs mean
+ *   [D], obs var [D], obs count, return accumulator, return mean, var, count} (initially 0, 1,
+ *   1e-4, 0, 0, 1, 1e-4). obs [N, D]: the returned observation (the reset one of a done env);
+ *   final_obs [N, D]: the terminal one, normalised first for done envs (two updates), NULL with
+ *   both flag arrays NULL; reward [N] or NULL (a reset); terminated / truncated [N] (!= 0) or
+ *   NULL; ret = ret * gamma * (1 - terminated) + reward. A flag of 0 copies that output through.
+ * ocppo_pendulum_step: Pendulum-v1 (gymnasium 0.28.1 dynamics, f64) behind ClipAction and
+ *   TimeLimit(200), same-step auto-reset. actions [N] f32 or NULL = reset; state [N, 2] f64;
+ *   counters [N, 2] i64 {elapsed, episodes}; obs_out [N, 3]; final_obs_out [N, 3] or NULL;
+ *   reward_out / done_out [N]; ep_state [N, 5] on the raw reward or NULL; reset states from
+ *   ocppo_cartpole_step's stream. norm_state != NULL: the outputs pass through
+ *   ocppo_env_normalize's chain in the same launch, bitwise the two launches.
+ * Contract: 1 <= A <= 64, M >= 1, D >= 1, N <= 2^20, 0 <= gamma <= 1.
+ * ------------------------------------------------------------------------------------------- */
+OCPPO_API int ocppo_gauss_head_sample(ocppo_stream_t stream, const float* mean,
+                                      const float* logstd, const float* z, const float* value_in,
+                                      int64_t N, int64_t A, float* action, float* logprob,
+                                      float* value);
+OCPPO_API int ocppo_gauss_ppo_loss_fwd_bwd(
+    ocppo_stream_t stream, const float* mean, const float* logstd, const float* new_value,
+    int64_t M, int64_t A, const float* actions, const float* logprobs, const float* advantages,
+    const float* returns, const float* values, const float* adv_stats, double clip_coef,
+    double ent_coef, double vf_coef, int norm_adv, int clip_vloss, uint64_t seed,
+    const int64_t* rpo_counter, int64_t mb, double rpo_alpha, float* dmean, float* dvalue,
+    float* dlogstd, float* stats);
+OCPPO_API int ocppo_rpo_noise(ocppo_stream_t stream, uint64_t seed, const int64_t* rpo_counter,
+                              int64_t mb, int64_t M, int64_t A, double rpo_alpha, float* out);
+OCPPO_API int ocppo_env_normalize(ocppo_stream_t stream, const float* obs, const float* final_obs,
+                                  const float* reward, const float* terminated,
+                                  const float* truncated, int64_t N, int64_t D, double* norm_state,
+                                  int norm_obs, int norm_reward, double gamma, float* obs_out,
+                                  float* reward_out);
+OCPPO_API int ocppo_pendulum_step(ocppo_stream_t stream, uint64_t seed, const float* actions,
+                                  int64_t N, double* state, int64_t* counters, float* obs_out,
+                                  float* final_obs_out, float* reward_out, float* done_out,
+                                  float* ep_state, double* norm_state, int norm_obs,
+                                  int norm_reward, double gamma);
 
 #ifdef __cplusplus
 }

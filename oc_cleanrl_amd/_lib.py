@@ -22,7 +22,7 @@ LIB_PATH = Path(os.environ.get("OCPPO_LIB", PKG / "lib" / "libocppo_hip.so"))
 HEADER = PKG.parent / "include" / "ocppo.h"
 
 # constants mirrored from include/ocppo.h (checked against the header by tests/test_abi.py)
-OCPPO_ABI_VERSION = 40
+OCPPO_ABI_VERSION = 41
 OCPPO_OK, OCPPO_E_INVALID, OCPPO_E_LAUNCH, OCPPO_E_WORKSPACE = 0, 1, 2, 3
 OCPPO_F32, OCPPO_BF16, OCPPO_U8 = 0, 1, 2
 OCPPO_X6_MBITS_ROWS = 2
@@ -188,6 +188,12 @@ SIGNATURES: dict[str, tuple[type, list]] = {
     "ocppo_pqn_head_loss_fwd_bwd": (I, [P, P, P, P, P, P, I64, I64, I64, P, P, P, P, P, SZ]),
     "ocppo_qdagger_loss_fwd_bwd": (I, [P, P, P, P, P, P, P, I64, I64, D, D, P, P, P]),
     "ocppo_qdagger_episode_push": (I, [P, P, P, I64, P, P, P, D, P]),
+    "ocppo_gauss_head_sample": (I, [P, P, P, P, P, I64, I64, P, P, P]),
+    "ocppo_gauss_ppo_loss_fwd_bwd": (I, [P, P, P, P, I64, I64, P, P, P, P, P, P, D, D, D, I, I,
+                                         U64, P, I64, D, P, P, P, P]),
+    "ocppo_rpo_noise": (I, [P, U64, P, I64, I64, I64, D, P]),
+    "ocppo_env_normalize": (I, [P, P, P, P, P, P, I64, I64, P, I, I, D, P, P]),
+    "ocppo_pendulum_step": (I, [P, U64, P, I64, P, P, P, P, P, P, P, P, I, I, D]),
 }
 
 

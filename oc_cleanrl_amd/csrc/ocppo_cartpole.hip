@@ -33,8 +33,7 @@ constexpr int64_t kMaxSteps = 500;
 // uniform(-0.05, 0.05) as numpy computes low + (high - low) * u, u a 53-bit double in [0, 1)
 __device__ __forceinline__ void cartpole_reset_state(uint64_t seed, int64_t n, int64_t episode,
                                                      double* st) {
-  const uint64_t key = splitmix64(splitmix64(seed) + static_cast<uint64_t>(n) * 0x100000001B3ull) ^
-                       splitmix64(static_cast<uint64_t>(episode) + 0x632BE59BD9B4E019ull);
+  const uint64_t key = env_reset_key(seed, n, episode);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const uint64_t h = splitmix64(key + static_cast<uint64_t>(i));

@@ -22,6 +22,13 @@ __device__ __forceinline__ double unit53(uint64_t h) {
   return static_cast<double>(h >> 11) * (1.0 / 9007199254740992.0);
 }
 
+// The classic-control envs' reset stream: the key of env n's episode; draw i of that reset is
+// unit53(splitmix64(key + i)) (CartPole's four state values, Pendulum's two).
+__device__ __forceinline__ uint64_t env_reset_key(uint64_t seed, int64_t n, int64_t episode) {
+  return splitmix64(splitmix64(seed) + static_cast<uint64_t>(n) * 0x100000001B3ull) ^
+         splitmix64(static_cast<uint64_t>(episode) + 0x632BE59BD9B4E019ull);
+}
+
 // epsilon-greedy (dqn_atari_oc.py:345-350, c51_atari_oc.py:303-308): epsilon = max(slope * t +
 // start_e, end_e) with slope = (end_e - start_e) / duration (linear_schedule, :230-232, all in
 // double), ONE coin per global step t for all envs (the reference's `random.random() < epsilon`

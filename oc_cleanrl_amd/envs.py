@@ -116,12 +116,90 @@ class CartPoleVecEnv:
         return s
 
 
+class PendulumVecEnv:
+    """num_envs Pendulum-v1 envs on one device behind the wrapper chain of
+    cleanrl/ppo_continuous_action.py:95-100 (RecordEpisodeStatistics, ClipAction,
+    NormalizeObservation, clip, NormalizeReward(gamma), clip), stepped by one HIP kernel
+    (ops.pendulum_step: gymnasium 0.28.1 dynamics in f64, TimeLimit 200, same-step auto-reset,
+    every env with normalisation statistics of its own as in SyncVectorEnv).
+
+    CartPoleVecEnv's interface with a float action: step() takes actions [N, 1] f32; frame [N, 3]
+    f32 is the normalised observation, reward [N] the normalised reward, ep_state counts the raw
+    rewards. fused=False runs the raw step and ops.env_normalize as two launches (bitwise the
+    same)."""
+
+    pixels = False
+    integer_obs = False
+    continuous = True
+
+    def __init__(self, num_envs: int, seed: int, device, gamma: float = 0.99,
+                 norm_obs: bool = True, norm_reward: bool = True, fused: bool = True):
+        self.env_id = "Pendulum-v1"
+        self.num_envs = N = num_envs
+        self.n_actions = 1  # action dimensions
+        self.window = 1
+        self.frame_elems = 3
+        self.single_obs_shape = (1, 3)
+        self.frame_dtype = torch.float32
+        self.seed = int(seed)
+        self.device = torch.device(device)
+        self.gamma, self.norm_obs, self.norm_reward = float(gamma), norm_obs, norm_reward
+        self.fused = fused
+        f32 = torch.float32
+        self.state = torch.zeros((N, 2), dtype=torch.float64, device=device)
+        self.counters = torch.zeros((N, 2), dtype=torch.int64, device=device)
+        self.norm_state = ops.cont_norm_state(N, 3, device)
+        self.frame = torch.zeros((N, 3), dtype=f32, device=device)
+        self.reward = torch.zeros(N, dtype=f32, device=device)
+        self.done = torch.zeros(N, dtype=f32, device=device)
+        self.ep_state = torch.zeros((N, 5), dtype=f32, device=device)
+        # the two-launch form's raw outputs
+        self.raw_frame = torch.zeros((N, 3), dtype=f32, device=device)
+        self.final_frame = torch.zeros((N, 3), dtype=f32, device=device)
+        self.raw_reward = torch.zeros(N, dtype=f32, device=device)
+
+    def _norm(self):
+        return dict(gamma=self.gamma, norm_obs=self.norm_obs, norm_reward=self.norm_reward)
+
+    def reset(self):
+        if self.fused:
+            ops.pendulum_step(self.seed, None, self.state, self.counters, self.frame,
+                              norm_state=self.norm_state, **self._norm())
+        else:
+            ops.pendulum_step(self.seed, None, self.state, self.counters, self.raw_frame)
+            ops.env_normalize(self.raw_frame, self.norm_state, self.frame, **self._norm())
+        return self.frame
+
+    def step(self, actions, step_offset: int = 0):
+        if self.fused:
+            ops.pendulum_step(self.seed, actions, self.state, self.counters, self.frame,
+                              self.reward, self.done, self.ep_state, norm_state=self.norm_state,
+                              **self._norm())
+            return
+        ops.pendulum_step(self.seed, actions, self.state, self.counters, self.raw_frame,
+                          self.raw_reward, self.done, self.ep_state,
+                          final_obs_out=self.final_frame)
+        ops.env_normalize(self.raw_frame, self.norm_state, self.frame, self.raw_reward,
+                          self.reward, self.final_frame, truncated=self.done, **self._norm())
+
+    def advance(self, n: int):
+        pass
+
+    def pop_episode_stats(self):
+        s = self.ep_state[:, 2:5].sum(0, dtype=torch.float64).tolist()
+        self.ep_state[:, 2:5].zero_()
+        return s
+
+
 def make_device_env(env_id: str, obs_mode: str, num_envs: int, num_features: int, seed: int,
-                    device, window: int = 4):
-    """The device-resident vector env for `env_id`: CartPole-v1 (config 1) or the synthetic
-    Atari env (configs 2-5; ALE / OCAtari are not available)."""
+                    device, window: int = 4, gamma: float = 0.99):
+    """The device-resident vector env for `env_id`: CartPole-v1 (config 1), Pendulum-v1 (the
+    continuous-action learners; gamma: its NormalizeReward's discount) or the synthetic Atari env
+    (configs 2-5; ALE / OCAtari are not available)."""
     if env_id == "CartPole-v1":
         return CartPoleVecEnv(num_envs, seed, device)
+    if env_id == "Pendulum-v1":
+        return PendulumVecEnv(num_envs, seed, device, gamma=gamma)
     return SyntheticAtariEnv(env_id, obs_mode, num_envs, num_features, seed, device, window)
 
 

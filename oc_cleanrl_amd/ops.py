@@ -3884,3 +3884,154 @@ def qdagger_episode_push(reward, done, ring: EpisodeRing, teacher_mean: float):
          _check(ring.state, "ring_state", torch.int64, dev, 2), teacher_mean,
          _check(ring.coeff, "coeff_out", f, dev, 1))
     return ring.coeff
+
+
+# ---------------------------------------------------------------------------------------------
+# Continuous-action PPO / RPO (ppo_continuous_action.py, rpo_continuous_action.py): the Gaussian
+# head's sample, the fused loss, the wrapper chain and Pendulum-v1 (csrc/ocppo_contppo.hip)
+# ---------------------------------------------------------------------------------------------
+GAUSS_MAX_ACTIONS = 64
+
+
+def _gauss_shape(mean, logstd, who: str):
+    if mean.dim() != 2 or mean.shape[1] < 1:
+        raise ValueError(f"{who}: mean must be [rows, A >= 1], got {tuple(mean.shape)}")
+    R, A = mean.shape
+    if A > GAUSS_MAX_ACTIONS:
+        raise ValueError(f"{who}: A = {A} action dimensions, at most {GAUSS_MAX_ACTIONS}")
+    if logstd.numel() != A:
+        raise ValueError(f"{who}: logstd has {logstd.numel()} elements, expected A = {A}")
+    return R, A
+
+
+def gauss_head_sample(mean, logstd, z, value_in, action=None, logprob=None, value=None):
+    """probs.sample() and log_prob(action).sum(1) of ppo_continuous_action.py:134-141 for mean
+    [N, A], logstd [A] (or [1, A]) and standard normal draws z [N, A]: action = z * exp(logstd) +
+    mean (bitwise torch's z.mul(std).add(mean)), logprob [N] summed in column order, value [N] =
+    value_in. One launch."""
+    N, A = _gauss_shape(mean, logstd, "gauss_head_sample")
+    dev, f = mean.device, torch.float32
+    pm = _check(mean, "mean", f)
+    if action is None:
+        action = torch.empty_like(mean)
+    if logprob is None:
+        logprob = torch.empty(N, dtype=f, device=dev)
+    if value is None:
+        value = torch.empty(N, dtype=f, device=dev)
+    call("ocppo_gauss_head_sample", _stream(dev), pm, _check(logstd, "logstd", f, dev, A),
+         _check(z, "z", f, dev, N * A), _check(value_in, "value_in", f, dev, N), N, A,
+         _check(action, "action", f, dev, N * A), _check(logprob, "logprob", f, dev, N),
+         _check(value, "value", f, dev, N))
+    return action, logprob, value
+
+
+def rpo_counter(device):
+    """The device update counter of the RPO noise stream (i64 [1], zero)."""
+    return torch.zeros(1, dtype=torch.int64, device=device)
+
+
+def gauss_ppo_loss_fwd_bwd(mean, logstd, new_value, actions, logprobs, advantages, returns,
+                           values, *, adv_stats=None, clip_coef: float, ent_coef: float,
+                           vf_coef: float, norm_adv: bool, clip_vloss: bool, seed: int = 0,
+                           counter=None, mb: int = 0, rpo_alpha: float = 0.0, dmean=None,
+                           dvalue=None, dlogstd=None, stats=None):
+    """ppo_continuous_action.py:265-300 from the network outputs on, with the backward, in one
+    launch: (stats [9] in STAT_NAMES' layout, dmean [M, A], dvalue [M], dlogstd [A]). rpo_alpha >
+    0: uniform noise in [-alpha, alpha) is added to the mean before the log-prob
+    (rpo_continuous_action.py:138-141), drawn from the library's stream at (seed, counter
+    (rpo_counter), mb, row, column) -- rpo_noise returns the same draws."""
+    M, A = _gauss_shape(mean, logstd, "gauss_ppo_loss_fwd_bwd")
+    dev, f = mean.device, torch.float32
+    pm = _check(mean, "mean", f)
+    rpo_alpha = float(rpo_alpha)
+    if rpo_alpha < 0:
+        raise ValueError(f"gauss_ppo_loss_fwd_bwd: rpo_alpha = {rpo_alpha} must not be negative")
+    if rpo_alpha > 0 and counter is None:
+        raise ValueError("gauss_ppo_loss_fwd_bwd: rpo_alpha > 0 needs the device counter")
+    if dmean is None:
+        dmean = torch.empty_like(mean)
+    if dvalue is None:
+        dvalue = torch.empty(M, dtype=f, device=dev)
+    if dlogstd is None:
+        dlogstd = torch.empty(A, dtype=f, device=dev)
+    if stats is None:
+        stats = torch.empty(len(STAT_NAMES), dtype=f, device=dev)
+    call("ocppo_gauss_ppo_loss_fwd_bwd", _stream(dev), pm, _check(logstd, "logstd", f, dev, A),
+         _check(new_value, "new_value", f, dev, M), M, A, _check(actions, "actions", f, dev, M * A),
+         _check(logprobs, "logprobs", f, dev, M), _check(advantages, "advantages", f, dev, M),
+         _check(returns, "returns", f, dev, M), _check(values, "values", f, dev, M),
+         _opt(adv_stats, "adv_stats", f, dev, 2) if norm_adv else None, float(clip_coef),
+         float(ent_coef), float(vf_coef), int(bool(norm_adv)), int(bool(clip_vloss)),
+         int(seed) & 0xFFFFFFFFFFFFFFFF, _opt(counter, "counter", torch.int64, dev, 1), int(mb),
+         rpo_alpha, _check(dmean, "dmean", f, dev, M * A), _check(dvalue, "dvalue", f, dev, M),
+         _check(dlogstd, "dlogstd", f, dev, A), _check(stats, "stats", f, dev, len(STAT_NAMES)))
+    return stats, dmean, dvalue, dlogstd
+
+
+def rpo_noise(seed: int, counter, mb: int, M: int, A: int, alpha: float, out=None):
+    """The [M, A] draws gauss_ppo_loss_fwd_bwd adds to the mean at (seed, counter, mb)."""
+    dev = counter.device
+    if not 1 <= A <= GAUSS_MAX_ACTIONS:
+        raise ValueError(f"rpo_noise: A = {A}, expected 1..{GAUSS_MAX_ACTIONS}")
+    if out is None:
+        out = torch.empty((M, A), dtype=torch.float32, device=dev)
+    call("ocppo_rpo_noise", _stream(dev), int(seed) & 0xFFFFFFFFFFFFFFFF,
+         _check(counter, "counter", torch.int64, dev, 1), int(mb), M, A, float(alpha),
+         _check(out, "out", torch.float32, dev, M * A))
+    return out
+
+
+def cont_norm_state(N: int, D: int, device):
+    """The wrapper chain's per-env statistics [N, 2D + 5] f64: the observation RunningMeanStd
+    (mean [D] zeros, var [D] ones, count 1e-4), the return accumulator (0) and the return
+    RunningMeanStd (0, 1, 1e-4)."""
+    st = torch.zeros((N, 2 * D + 5), dtype=torch.float64, device=device)
+    st[:, D:2 * D] = 1.0
+    st[:, 2 * D] = 1e-4
+    st[:, 2 * D + 3] = 1.0
+    st[:, 2 * D + 4] = 1e-4
+    return st
+
+
+def env_normalize(obs, state, obs_out, reward=None, reward_out=None, final_obs=None,
+                  terminated=None, truncated=None, gamma: float = 0.99, norm_obs: bool = True,
+                  norm_reward: bool = True):
+    """The wrapper chain of ppo_continuous_action.py:96-100 on N envs' raw step outputs (obs
+    [N, D], reward [N], terminated / truncated [N] f32, final_obs [N, D] = the terminal
+    observations of the done envs) with per-env statistics `state` (cont_norm_state): obs_out
+    [N, D], reward_out [N]. reward None: a reset (observation path only). One launch."""
+    if obs.dim() != 2 or obs.shape[1] < 1:
+        raise ValueError(f"env_normalize: obs must be [N, D >= 1], got {tuple(obs.shape)}")
+    N, D = obs.shape
+    dev, f = obs.device, torch.float32
+    po = _check(obs, "obs", f)
+    if (terminated is not None or truncated is not None) and final_obs is None:
+        raise ValueError("env_normalize: done flags need final_obs")
+    call("ocppo_env_normalize", _stream(dev), po, _opt(final_obs, "final_obs", f, dev, N * D),
+         _opt(reward, "reward", f, dev, N), _opt(terminated, "terminated", f, dev, N),
+         _opt(truncated, "truncated", f, dev, N), N, D,
+         _check(state, "state", torch.float64, dev, N * (2 * D + 5)), int(bool(norm_obs)),
+         int(bool(norm_reward)), float(gamma), _check(obs_out, "obs_out", f, dev, N * D),
+         _opt(reward_out, "reward_out", f, dev, N))
+    return obs_out, reward_out
+
+
+def pendulum_step(seed: int, actions, state, counters, obs_out, reward_out=None, done_out=None,
+                  ep_state=None, final_obs_out=None, norm_state=None, norm_obs: bool = True,
+                  norm_reward: bool = True, gamma: float = 0.99):
+    """One step (actions [N] or [N, 1] f32 torques) or, with actions None, a reset of N device
+    Pendulum-v1 envs (gymnasium 0.28.1 dynamics, ClipAction, TimeLimit 200, same-step auto-reset):
+    state [N, 2] f64 and counters [N, 2] i64 in/out, obs_out [N, 3] f32, reward_out / done_out [N]
+    f32, final_obs_out [N, 3] the terminal observations. norm_state (cont_norm_state(N, 3)): the
+    outputs pass through env_normalize's chain in the same launch."""
+    N = obs_out.shape[0]
+    dev, f = obs_out.device, torch.float32
+    call("ocppo_pendulum_step", _stream(dev), int(seed) & 0xFFFFFFFFFFFFFFFF,
+         _opt(actions, "actions", f, dev, N), N, _check(state, "state", torch.float64, dev, 2 * N),
+         _check(counters, "counters", torch.int64, dev, 2 * N),
+         _check(obs_out, "obs_out", f, dev, 3 * N),
+         _opt(final_obs_out, "final_obs_out", f, dev, 3 * N),
+         _opt(reward_out, "reward_out", f, dev, N), _opt(done_out, "done_out", f, dev, N),
+         _opt(ep_state, "ep_state", f, dev, 5 * N),
+         _opt(norm_state, "norm_state", torch.float64, dev, 11 * N), int(bool(norm_obs)),
+         int(bool(norm_reward)), float(gamma))

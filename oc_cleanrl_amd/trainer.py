@@ -326,8 +326,7 @@ class PPOTrainer:
                                   a.buffer_window_size)
             self.env.reset()  # the obs shape comes from the env
         else:
-            self.env = make_device_env(a.env_id, a.obs_mode, self.N, a.num_features, self.seed,
-                                       self.dev, a.buffer_window_size)
+            self.env = self._make_env()
         self.pixels = self.env.pixels
         # a host env's reset observations are its own stacks (envs.HostVecEnv): the stored obs no
         # longer follow the frame-stack fill rule the rollout frame cache and the update's frame
@@ -523,6 +522,12 @@ class PPOTrainer:
         self.global_step = 0
         self.last_metrics: dict = {}
         self._reset_env()
+
+    def _make_env(self):
+        """The device-resident vector env of this rank (subclasses build or take another one)."""
+        a = self.args
+        return make_device_env(a.env_id, a.obs_mode, self.N, a.num_features, self.seed, self.dev,
+                               a.buffer_window_size)
 
     def _make_agent(self) -> nn.Module:
         """The agent this trainer trains (on the CPU; subclasses build another one)."""
