@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCPPO_ABI_VERSION 41
+#define OCPPO_ABI_VERSION 42
 
 /* status codes */
 #define OCPPO_OK 0
@@ -1711,6 +1711,83 @@ OCPPO_API int ocppo_pendulum_step(ocppo_stream_t stream, uint64_t seed, const fl
                                   float* final_obs_out, float* reward_out, float* done_out,
                                   float* ep_state, double* norm_state, int norm_obs,
                                   int norm_reward, double gamma);
+
+/* ---------------------------------------------------------------------------------------------
+ * TD3 / DDPG (cleanrl/td3_continuous_action.py, ddpg_continuous_action.py), ABI 42: a
+ * deterministic policy over float-vector actions, 1 <= A <= 64. All f32 unless stated, no atomics
+ * (the batch sums are f64 in a fixed order: bitwise repeatable), graph-capturable, one launch each
+ * (the sample: two). scale / bias / low / high are device arrays [A].
+ *
+ * ocppo_cont_replay_add / _sample: SB3 ReplayBuffer(optimize_memory_usage=False,
+ *   handle_timeout_termination=False): rb_obs, rb_next_obs [size, E, D], rb_actions [size, E, A],
+ *   rb_rewards, rb_dones [size, E], state = device int64 {pos, full}. add stores final_obs in the
+ *   rows whose done != 0 (final_obs and done both NULL: none) and terminated (NULL: 0) as the done
+ *   flag; carry != 0: obs <- next_obs afterwards. sample draws B (row, env) pairs uniformly over
+ *   the filled rows from the stream keyed by (seed, counter[0], b), writes obs_act [B, D + A] =
+ *   cat(obs, action), the observation columns of next_obs_act [B, D + A] (its action columns are
+ *   left for ocppo_td3_target_actions), rewards_out, dones_out [B], indices_out [B, 2] or NULL,
+ *   then counter[0] += 1.
+ * ocppo_td3_act (:205-211) at global step t = step[0] + step_offset: t < learning_starts: uniform
+ *   in [low, high) per dimension; else clip(tanh(hidden W^T + b) * scale + bias + (scale *
+ *   exploration_noise) * z, low, high), hidden [E, H], w_mu [A, H], z a Box-Muller normal in f32.
+ *   Draws: Philox4x32-10 keyed by (seed, t, e, a). ocppo_td3_noise writes them: mode 0 z, mode 1
+ *   the uniform phase's u in [0, 1), both [rows, A] at t = counter[0] + offset; mode 2 the target
+ *   stream's z at sample counter counter[0] + offset.
+ * ocppo_td3_target_actions (:239-245): mu [B, A] (the target actor's output before tanh) ->
+ *   next_obs_act[:, D:] = clamp(tanh(mu) * scale + bias + clamp(z * policy_noise, +-noise_clip) *
+ *   scale, low0, high0); policy_noise == 0 (DDPG, :216): no stream, no clamp.
+ * ocppo_td3_critic_loss_fwd_bwd (:248-255): y = r + ((1 - d) * gamma) * min(q1t, q2t), dq = (2 /
+ *   B)(q - y), stats [4] = {qf1_loss, qf2_loss, mean q1, mean q2}; q2_next_target, q2, dq2 all
+ *   NULL: the single critic of ddpg_continuous_action.py:218-221. y_out [B] or NULL.
+ * ocppo_td3_policy_actions_fwd / _bwd (:263): xa [B, D + A] = obs_act with its action columns
+ *   replaced by tanh(mu) * scale + bias, tanh_out [B, A]; dmu = (dxa[:, D:] * scale) * (1 -
+ *   tanh^2).
+ * ocppo_polyak (:269-274): targets[k][i] = tau * params[k][i] + (1 - tau) * targets[k][i] for
+ *   1 <= n_pairs <= 4 flat buffers of numels[k] elements (host arrays): two rounded products and
+ *   one rounded add.
+ * ------------------------------------------------------------------------------------------- */
+OCPPO_API int ocppo_cont_replay_add(ocppo_stream_t stream, float* obs, const float* next_obs,
+                                    const float* final_obs, const float* done,
+                                    const float* actions, const float* rewards,
+                                    const float* terminated, int64_t E, int64_t D, int64_t A,
+                                    int64_t* state, int64_t size, float* rb_obs,
+                                    float* rb_next_obs, float* rb_actions, float* rb_rewards,
+                                    float* rb_dones, int carry);
+OCPPO_API int ocppo_cont_replay_sample(ocppo_stream_t stream, uint64_t seed, int64_t* counter,
+                                       const int64_t* state, int64_t size, int64_t E, int64_t D,
+                                       int64_t A, const float* rb_obs, const float* rb_next_obs,
+                                       const float* rb_actions, const float* rb_rewards,
+                                       const float* rb_dones, int64_t B, float* obs_act,
+                                       float* next_obs_act, float* rewards_out, float* dones_out,
+                                       int64_t* indices_out);
+OCPPO_API int ocppo_td3_act(ocppo_stream_t stream, const float* hidden, int64_t E, int64_t H,
+                            const float* w_mu, const float* b_mu, int64_t A,
+                            const float* action_scale, const float* action_bias, const float* low,
+                            const float* high, uint64_t seed, const int64_t* step,
+                            int64_t step_offset, int64_t learning_starts,
+                            double exploration_noise, float* actions);
+OCPPO_API int ocppo_td3_noise(ocppo_stream_t stream, uint64_t seed, const int64_t* counter,
+                              int64_t offset, int64_t rows, int64_t A, int mode, float* out);
+OCPPO_API int ocppo_td3_target_actions(ocppo_stream_t stream, const float* mu, int64_t B,
+                                       int64_t D, int64_t A, const float* action_scale,
+                                       const float* action_bias, uint64_t seed,
+                                       const int64_t* counter, double policy_noise,
+                                       double noise_clip, double low0, double high0,
+                                       float* next_obs_act);
+OCPPO_API int ocppo_td3_critic_loss_fwd_bwd(ocppo_stream_t stream, const float* q1_next_target,
+                                            const float* q2_next_target, const float* q1,
+                                            const float* q2, const float* rewards,
+                                            const float* dones, int64_t B, double gamma,
+                                            float* dq1, float* dq2, float* stats, float* y_out);
+OCPPO_API int ocppo_td3_policy_actions_fwd(ocppo_stream_t stream, const float* mu,
+                                           const float* obs_act, int64_t B, int64_t D, int64_t A,
+                                           const float* action_scale, const float* action_bias,
+                                           float* xa, float* tanh_out);
+OCPPO_API int ocppo_td3_policy_actions_bwd(ocppo_stream_t stream, const float* dxa,
+                                           const float* tanh_in, int64_t B, int64_t D, int64_t A,
+                                           const float* action_scale, float* dmu);
+OCPPO_API int ocppo_polyak(ocppo_stream_t stream, int n_pairs, const float* const* params,
+                           float* const* targets, const int64_t* numels, double tau);
 
 #ifdef __cplusplus
 }

@@ -126,14 +126,18 @@ class PendulumVecEnv:
     CartPoleVecEnv's interface with a float action: step() takes actions [N, 1] f32; frame [N, 3]
     f32 is the normalised observation, reward [N] the normalised reward, ep_state counts the raw
     rewards. fused=False runs the raw step and ops.env_normalize as two launches (bitwise the
-    same)."""
+    same). raw=True is the env behind RecordEpisodeStatistics alone (td3_continuous_action.py's
+    make_env): frame / reward are the raw outputs and final_frame holds the terminal observations
+    of the envs whose `done` is set (Pendulum only truncates: nothing terminates)."""
 
     pixels = False
     integer_obs = False
     continuous = True
+    action_low, action_high = (-2.0,), (2.0,)  # the Box's bounds per action dimension
 
     def __init__(self, num_envs: int, seed: int, device, gamma: float = 0.99,
-                 norm_obs: bool = True, norm_reward: bool = True, fused: bool = True):
+                 norm_obs: bool = True, norm_reward: bool = True, fused: bool = True,
+                 raw: bool = False):
         self.env_id = "Pendulum-v1"
         self.num_envs = N = num_envs
         self.n_actions = 1  # action dimensions
@@ -145,6 +149,7 @@ class PendulumVecEnv:
         self.device = torch.device(device)
         self.gamma, self.norm_obs, self.norm_reward = float(gamma), norm_obs, norm_reward
         self.fused = fused
+        self.raw = raw
         f32 = torch.float32
         self.state = torch.zeros((N, 2), dtype=torch.float64, device=device)
         self.counters = torch.zeros((N, 2), dtype=torch.int64, device=device)
@@ -162,7 +167,9 @@ class PendulumVecEnv:
         return dict(gamma=self.gamma, norm_obs=self.norm_obs, norm_reward=self.norm_reward)
 
     def reset(self):
-        if self.fused:
+        if self.raw:
+            ops.pendulum_step(self.seed, None, self.state, self.counters, self.frame)
+        elif self.fused:
             ops.pendulum_step(self.seed, None, self.state, self.counters, self.frame,
                               norm_state=self.norm_state, **self._norm())
         else:
@@ -171,6 +178,11 @@ class PendulumVecEnv:
         return self.frame
 
     def step(self, actions, step_offset: int = 0):
+        if self.raw:
+            ops.pendulum_step(self.seed, actions, self.state, self.counters, self.frame,
+                              self.reward, self.done, self.ep_state,
+                              final_obs_out=self.final_frame)
+            return
         if self.fused:
             ops.pendulum_step(self.seed, actions, self.state, self.counters, self.frame,
                               self.reward, self.done, self.ep_state, norm_state=self.norm_state,

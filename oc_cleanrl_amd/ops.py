@@ -4035,3 +4035,247 @@ def pendulum_step(seed: int, actions, state, counters, obs_out, reward_out=None,
          _opt(ep_state, "ep_state", f, dev, 5 * N),
          _opt(norm_state, "norm_state", torch.float64, dev, 11 * N), int(bool(norm_obs)),
          int(bool(norm_reward)), float(gamma))
+
+
+# ---------------------------------------------------------------------------------------------
+# TD3 / DDPG (td3_continuous_action.py, ddpg_continuous_action.py): float-action replay, acting,
+# the smoothed target action, the critic loss, the actor loss's action and the soft target update
+# (csrc/ocppo_td3.hip)
+# ---------------------------------------------------------------------------------------------
+class ContReplayBuffer:
+    """SB3 ReplayBuffer(optimize_memory_usage=False, handle_timeout_termination=False) in HBM for
+    float-vector actions (td3_continuous_action.py:191-198): obs, next_obs [size, E, D], actions
+    [size, E, A], rewards, dones [size, E], all f32; {pos, full} and the sample counter on the
+    device, so add / sample are graph-replayable. A sampled batch is the critics' input:
+    obs_act [B, D + A] = cat(observations, actions) and next_obs_act [B, D + A] whose action
+    columns td3_target_actions fills; `observations` / `next_observations` / `actions` are views."""
+
+    def __init__(self, size: int, n_envs: int, obs_dim: int, action_dim: int, device,
+                 seed: int = 0):
+        self.size, self.E, self.D, self.A = int(size), int(n_envs), int(obs_dim), int(action_dim)
+        if self.size < 1 or self.E < 1 or self.D < 1 or not 1 <= self.A <= GAUSS_MAX_ACTIONS:
+            raise ValueError(f"ContReplayBuffer: size={size} E={n_envs} D={obs_dim} A={action_dim}"
+                             f" (all >= 1, A <= {GAUSS_MAX_ACTIONS})")
+        dev = self.device = torch.device(device)
+        z = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)  # noqa: E731
+        self.obs, self.next_obs = z(self.size, self.E, self.D), z(self.size, self.E, self.D)
+        self.actions = z(self.size, self.E, self.A)
+        self.rewards, self.dones = z(self.size, self.E), z(self.size, self.E)
+        self.state = torch.zeros(2, dtype=torch.int64, device=dev)  # pos, full
+        self.counter = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+
+    def add(self, obs, next_obs, final_obs, done, actions, rewards, terminated=None,
+            carry: bool = False):
+        """rb.add(obs, real_next_obs, actions, rewards, terminations) of :226-230: real_next_obs =
+        final_obs where done else next_obs. carry: obs <- next_obs afterwards (:233)."""
+        dev, f = self.device, torch.float32
+        if (final_obs is None) != (done is None):
+            raise ValueError("ContReplayBuffer.add: final_obs and done come together")
+        n = self.E * self.D
+        call("ocppo_cont_replay_add", _stream(dev), _check(obs, "obs", f, dev, n),
+             _check(next_obs, "next_obs", f, dev, n), _opt(final_obs, "final_obs", f, dev, n),
+             _opt(done, "done", f, dev, self.E), _check(actions, "actions", f, dev, self.E * self.A),
+             _check(rewards, "rewards", f, dev, self.E),
+             _opt(terminated, "terminated", f, dev, self.E), self.E, self.D, self.A,
+             self.state.data_ptr(), self.size, self.obs.data_ptr(), self.next_obs.data_ptr(),
+             self.actions.data_ptr(), self.rewards.data_ptr(), self.dones.data_ptr(),
+             int(bool(carry)))
+
+    def batch(self, batch_size: int, with_indices: bool = False) -> dict:
+        """Output buffers of one sample (and the strided views of them)."""
+        B, D, dev = int(batch_size), self.D, self.device
+        z = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)  # noqa: E731
+        out = {"obs_act": z(B, D + self.A), "next_obs_act": z(B, D + self.A),
+               "rewards": z(B, 1), "dones": z(B, 1)}
+        out["observations"] = out["obs_act"][:, :D]
+        out["actions"] = out["obs_act"][:, D:]
+        out["next_observations"] = out["next_obs_act"][:, :D]
+        if with_indices:
+            out["indices"] = torch.zeros((B, 2), dtype=torch.int64, device=dev)
+        return out
+
+    def sample(self, batch_size: int, out: dict | None = None, with_indices: bool = False):
+        dev, f = self.device, torch.float32
+        B = int(batch_size)
+        if B < 1:
+            raise ValueError(f"ContReplayBuffer.sample: batch_size = {B}")
+        if out is None:
+            out = self.batch(B, with_indices)
+        n = B * (self.D + self.A)
+        call("ocppo_cont_replay_sample", _stream(dev), self.seed, self.counter.data_ptr(),
+             self.state.data_ptr(), self.size, self.E, self.D, self.A, self.obs.data_ptr(),
+             self.next_obs.data_ptr(), self.actions.data_ptr(), self.rewards.data_ptr(),
+             self.dones.data_ptr(), B, _check(out["obs_act"], "obs_act", f, dev, n),
+             _check(out["next_obs_act"], "next_obs_act", f, dev, n),
+             _check(out["rewards"], "rewards", f, dev, B), _check(out["dones"], "dones", f, dev, B),
+             _check(out["indices"], "indices", torch.int64, dev, 2 * B) if "indices" in out
+             else None)
+        return out
+
+
+def _td3_vec(t, name: str, A: int, dev):
+    return _check(t, name, torch.float32, dev, A)
+
+
+def td3_act(hidden, w_mu, b_mu, action_scale, action_bias, low, high, seed: int, step,
+            learning_starts: int, exploration_noise: float, actions_out=None,
+            step_offset: int = 0):
+    """td3_continuous_action.py:205-211 at global step t = step[0] + step_offset, from the actor's
+    last hidden [E, H]: t < learning_starts: uniform in [low, high) per dimension; otherwise
+    clip(tanh(hidden @ w_mu.T + b_mu) * scale + bias + (scale * exploration_noise) * z, low, high).
+    One launch; the branch is taken on the device. td3_noise returns z (and the uniform u)."""
+    if hidden.dim() != 2 or w_mu.dim() != 2 or w_mu.shape[1] != hidden.shape[1]:
+        raise ValueError(f"td3_act: hidden {tuple(hidden.shape)} against w_mu {tuple(w_mu.shape)}")
+    E, H = hidden.shape
+    A = w_mu.shape[0]
+    if not 1 <= A <= GAUSS_MAX_ACTIONS:
+        raise ValueError(f"td3_act: A = {A} action dimensions, at most {GAUSS_MAX_ACTIONS}")
+    dev, f = hidden.device, torch.float32
+    if actions_out is None:
+        actions_out = torch.empty((E, A), dtype=f, device=dev)
+    call("ocppo_td3_act", _stream(dev), _check(hidden, "hidden", f), E, H,
+         _check(w_mu, "w_mu", f, dev, A * H), _check(b_mu, "b_mu", f, dev, A), A,
+         _td3_vec(action_scale, "action_scale", A, dev), _td3_vec(action_bias, "action_bias", A, dev),
+         _td3_vec(low, "low", A, dev), _td3_vec(high, "high", A, dev),
+         int(seed) & 0xFFFFFFFFFFFFFFFF, _check(step, "step", torch.int64, dev, 1),
+         int(step_offset), int(learning_starts), float(exploration_noise),
+         _check(actions_out, "actions", f, dev, E * A))
+    return actions_out
+
+
+def _td3_draws(seed: int, counter, offset: int, rows: int, A: int, mode: int, out):
+    dev = counter.device
+    if not 1 <= A <= GAUSS_MAX_ACTIONS:
+        raise ValueError(f"td3 noise: A = {A}, expected 1..{GAUSS_MAX_ACTIONS}")
+    if out is None:
+        out = torch.empty((rows, A), dtype=torch.float32, device=dev)
+    call("ocppo_td3_noise", _stream(dev), int(seed) & 0xFFFFFFFFFFFFFFFF,
+         _check(counter, "counter", torch.int64, dev, 1), int(offset), int(rows), A, mode,
+         _check(out, "out", torch.float32, dev, rows * A))
+    return out
+
+
+def td3_noise(seed: int, step, E: int, A: int, step_offset: int = 0, uniform: bool = False,
+              out=None):
+    """The [E, A] draws td3_act uses at global step step[0] + step_offset: the standard normal z,
+    or with `uniform` the random phase's u in [0, 1) (action = low + (high - low) * u)."""
+    return _td3_draws(seed, step, step_offset, E, A, 1 if uniform else 0, out)
+
+
+def td3_target_noise(seed: int, counter, B: int, A: int, offset: int = 0, out=None):
+    """The [B, A] standard normal draws td3_target_actions uses at sample counter counter[0] +
+    offset (the replay's counter after the sample: offset 0)."""
+    return _td3_draws(seed, counter, offset, B, A, 2, out)
+
+
+def td3_target_actions(mu, action_scale, action_bias, next_obs_act, seed: int = 0, counter=None,
+                       policy_noise: float = 0.0, noise_clip: float = 0.0, low: float = 0.0,
+                       high: float = 0.0):
+    """td3_continuous_action.py:239-245 from the target actor's pre-tanh output mu [B, A], into
+    the action columns of next_obs_act [B, D + A]: clamp(tanh(mu) * scale + bias + clamp(z *
+    policy_noise, -noise_clip, noise_clip) * scale, low, high) with the scalar bounds of the first
+    action dimension. policy_noise == 0 (ddpg_continuous_action.py:216): tanh(mu) * scale + bias."""
+    if mu.dim() != 2 or next_obs_act.dim() != 2 or next_obs_act.shape[0] != mu.shape[0] or \
+            next_obs_act.shape[1] <= mu.shape[1]:
+        raise ValueError(f"td3_target_actions: mu {tuple(mu.shape)} against next_obs_act "
+                         f"{tuple(next_obs_act.shape)}")
+    B, A = mu.shape
+    D = next_obs_act.shape[1] - A
+    dev, f = mu.device, torch.float32
+    if policy_noise != 0 and counter is None:
+        raise ValueError("td3_target_actions: policy_noise != 0 needs the device counter")
+    call("ocppo_td3_target_actions", _stream(dev), _check(mu, "mu", f), B, D, A,
+         _td3_vec(action_scale, "action_scale", A, dev), _td3_vec(action_bias, "action_bias", A, dev),
+         int(seed) & 0xFFFFFFFFFFFFFFFF, _opt(counter, "counter", torch.int64, dev, 1),
+         float(policy_noise), float(noise_clip), float(low), float(high),
+         _check(next_obs_act, "next_obs_act", f, dev, B * (D + A)))
+    return next_obs_act
+
+
+def td3_critic_loss_fwd_bwd(q1t, q2t, q1, q2, rewards, dones, gamma: float, dq1=None, dq2=None,
+                            stats=None, y_out=None):
+    """td3_continuous_action.py:248-255 from the four critic outputs [B] (or [B, 1]): (stats [4] =
+    {qf1_loss, qf2_loss, mean q1, mean q2}, dq1, dq2 = d qf_loss / d q). q2t = q2 = None: the
+    single critic of ddpg_continuous_action.py:218-221 (stats[1] = stats[3] = 0, dq2 None)."""
+    B = q1.numel()
+    dev, f = q1.device, torch.float32
+    twin = q2 is not None
+    if twin != (q2t is not None):
+        raise ValueError("td3_critic_loss_fwd_bwd: q2 and its target come together")
+    if dq1 is None:
+        dq1 = torch.empty_like(q1)
+    if twin and dq2 is None:
+        dq2 = torch.empty_like(q2)
+    if stats is None:
+        stats = torch.empty(4, dtype=f, device=dev)
+    call("ocppo_td3_critic_loss_fwd_bwd", _stream(dev), _check(q1t, "q1t", f, dev, B),
+         _opt(q2t, "q2t", f, dev, B), _check(q1, "q1", f, dev, B), _opt(q2, "q2", f, dev, B),
+         _check(rewards, "rewards", f, dev, B), _check(dones, "dones", f, dev, B), B, float(gamma),
+         _check(dq1, "dq1", f, dev, B), _check(dq2, "dq2", f, dev, B) if twin else None,
+         _check(stats, "stats", f, dev, 4), _opt(y_out, "y_out", f, dev, B))
+    return stats, dq1, (dq2 if twin else None)
+
+
+class _PolicyActions(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mu, obs_act, action_scale, action_bias):
+        B, A = mu.shape
+        D = obs_act.shape[1] - A
+        dev, f = mu.device, torch.float32
+        xa = torch.empty_like(obs_act)
+        th = torch.empty_like(mu)
+        call("ocppo_td3_policy_actions_fwd", _stream(dev), _check(mu, "mu", f), _check(
+            obs_act, "obs_act", f, dev, B * (D + A)), B, D, A,
+            _td3_vec(action_scale, "action_scale", A, dev),
+            _td3_vec(action_bias, "action_bias", A, dev), xa.data_ptr(), th.data_ptr())
+        ctx.save_for_backward(th, action_scale)
+        ctx.D = D
+        return xa
+
+    @staticmethod
+    def backward(ctx, dxa):
+        th, scale = ctx.saved_tensors
+        B, A = th.shape
+        dev = th.device
+        dxa = dxa.contiguous()
+        dmu = torch.empty_like(th)
+        call("ocppo_td3_policy_actions_bwd", _stream(dev),
+             _check(dxa, "dxa", torch.float32, dev, B * (ctx.D + A)), th.data_ptr(), B, ctx.D, A,
+             scale.data_ptr(), dmu.data_ptr())
+        return dmu, None, None, None
+
+
+def td3_policy_actions(mu, obs_act, action_scale, action_bias):
+    """The critic's input of the actor loss (td3_continuous_action.py:263): a [B, D + A] copy of
+    obs_act with its action columns replaced by tanh(mu) * scale + bias; differentiable in mu
+    (d mu = (dxa[:, D:] * scale) * (1 - tanh^2), two launches in all)."""
+    if mu.dim() != 2 or obs_act.dim() != 2 or obs_act.shape[0] != mu.shape[0] or \
+            obs_act.shape[1] <= mu.shape[1] or not 1 <= mu.shape[1] <= GAUSS_MAX_ACTIONS:
+        raise ValueError(f"td3_policy_actions: mu {tuple(mu.shape)} against obs_act "
+                         f"{tuple(obs_act.shape)}")
+    return _PolicyActions.apply(mu, obs_act, action_scale, action_bias)
+
+
+POLYAK_MAX_PAIRS = 4
+
+
+def polyak_(pairs, tau: float):
+    """target = tau * param + (1 - tau) * target for every (flat parameter, flat target) pair, in
+    place, one launch (td3_continuous_action.py:269-274): two rounded products and one rounded add
+    per element, bitwise `target.copy_(tau * param + (1.0 - tau) * target)`."""
+    pairs = list(pairs)
+    n = len(pairs)
+    if not 1 <= n <= POLYAK_MAX_PAIRS:
+        raise ValueError(f"polyak_: {n} pairs, expected 1..{POLYAK_MAX_PAIRS}")
+    dev = pairs[0][0].device
+    ps, ts, ns = [], [], []
+    for k, (p, t) in enumerate(pairs):
+        if p.numel() != t.numel():
+            raise ValueError(f"polyak_: pair {k}: {p.numel()} parameters, {t.numel()} targets")
+        ps.append(_check(p, f"param[{k}]", torch.float32, dev))
+        ts.append(_check(t, f"target[{k}]", torch.float32, dev))
+        ns.append(p.numel())
+    c = ctypes
+    call("ocppo_polyak", _stream(dev), n, (c.c_void_p * n)(*ps), (c.c_void_p * n)(*ts),
+         (c.c_int64 * n)(*ns), float(tau))
