@@ -211,6 +211,67 @@ def parse_args(argv=None, defaults: dict | None = None) -> Args:
     return parse_dataclass(Args, argv, defaults, "oc_cleanrl_amd PPO (ppo_atari_oc.py surface)")
 
 
+# What the learners on trainer.PPOTrainer other than ppo_atari_oc.py's own (lstm, pqn, pqn_lstm,
+# rnd, ppg, contppo) all leave off their command lines: the HackAtari / imperfect-detection
+# fields, the transformer's sizes, the PPObj-only rollout / update features, the final evaluation
+# and DP. A learner writes CORE_SKIP | {...}; a field of Args added later becomes a flag of every
+# learner unless it is named here or there.
+CORE_SKIP = frozenset({
+    "patch_size", "author", "test_modifs", "detection_failure_probability",
+    "mislabeling_probability", "noise_std", "extra_planes", "v2", "masked_wrapper", "add_pixels",
+    "rollout_frame_cache", "rollout_fusion", "rollout_cache_ring", "update_frame_dedup",
+    "x6_weight_planes", "emb_dim", "num_heads", "num_blocks", "eval_episodes", "dp_overlap",
+    "dp_exchange"})
+# ... and what PPOTrainer reads of those with a value other than Args' default: the features off
+CORE_FIXED = (("rollout_frame_cache", False), ("rollout_fusion", False),
+              ("rollout_cache_ring", False), ("update_frame_dedup", False),
+              ("x6_weight_planes", False), ("eval_episodes", 0), ("dp_overlap", False),
+              ("dp_exchange", False))
+
+
+def learner_args(name: str, doc: str, reference_fields, skip, own_defaults: dict | None = None,
+                 own_fields=(), fixed=()):
+    """The argument dataclass `name` of a learner on trainer.PPOTrainer. Its fields, in order: the
+    script's (`reference_fields`, (name, type, default) each), then every field of Args that the
+    script does not name and `skip` does not hold (Args' default unless `own_defaults` has one),
+    then the learner's `own_fields`. The skipped fields of Args stay readable as class attributes
+    (PPOTrainer reads some): Args' defaults, then the `fixed` (name, value) pairs."""
+    own_defaults = own_defaults or {}
+    named = {n for n, _, _ in reference_fields}
+    out = list(reference_fields)
+    for f in dataclasses.fields(Args):
+        if f.name not in named and f.name not in skip:
+            out.append((f.name, f.type, own_defaults.get(f.name, f.default)))
+    out += own_fields
+    cls = dataclasses.make_dataclass(name, [(n, t, field(default=d)) for n, t, d in out])
+    cls.__doc__ = doc
+    for f in dataclasses.fields(Args):
+        if f.name in skip:
+            setattr(cls, f.name, f.default)
+    for n, v in fixed:
+        setattr(cls, n, v)
+    return cls
+
+
+def check_sampling_noise(args):
+    if args.sampling_noise not in ("kernel", "head", "torch", "rollout"):
+        raise ValueError(f"sampling_noise must be kernel, head, torch or rollout, got "
+                         f"{args.sampling_noise!r}")
+
+
+def single_gpu_sizes(args, world_size: int, who: str):
+    """The derived sizes of a learner that runs on one GPU (`who`, e.g. "the PQN learner"): the
+    script's batch_size, minibatch_size and num_iterations, and the local_* names PPOTrainer
+    reads, equal to them."""
+    if world_size != 1:
+        raise NotImplementedError(f"world_size = {world_size}: {who} runs on one GPU")
+    args.world_size = 1
+    args.local_num_envs = args.num_envs
+    args.batch_size = args.local_batch_size = int(args.num_envs * args.num_steps)
+    args.minibatch_size = args.local_minibatch_size = int(args.batch_size // args.num_minibatches)
+    args.num_iterations = args.total_timesteps // args.batch_size
+
+
 def finalize(args: Args, world_size: int = 1) -> Args:
     """Derived sizes (ppo_atari_oc.py:344-356; DP: ppo_atari_multigpu.py:166-173)."""
     args.world_size = world_size
@@ -234,9 +295,7 @@ def finalize(args: Args, world_size: int = 1) -> Args:
         raise AssertionError('"obj" observations only work with "PPO_OBJ" architecture!')
     if args.local_batch_size % args.num_minibatches:
         raise ValueError("local batch size must be divisible by num_minibatches")
-    if args.sampling_noise not in ("kernel", "head", "torch", "rollout"):
-        raise ValueError(f"sampling_noise must be kernel, head, torch or rollout, got "
-                         f"{args.sampling_noise!r}")
+    check_sampling_noise(args)
     if args.dp_collectives not in ("rccl", "torch"):
         raise ValueError(f"dp_collectives must be rccl or torch, got {args.dp_collectives!r}")
     return args

@@ -20,7 +20,6 @@ latter); one randn per rollout instead of Normal.sample's draw per step; one GPU
 """
 from __future__ import annotations
 
-import dataclasses
 import math
 from typing import Optional
 
@@ -31,9 +30,9 @@ from torch.distributions.normal import Normal
 
 from . import ops
 from .agents import EnvSpec, Space, layer_init
-from .args import Args, env_rank, parse_dataclass
+from .args import CORE_FIXED, CORE_SKIP, learner_args, single_gpu_sizes
 from .envs import make_device_env
-from .trainer import PPOTrainer, run
+from .trainer import PPOTrainer, learner_main, run
 
 # The fused kernels (ops.gauss_head_sample, ops.gauss_ppo_loss_fwd_bwd); False: plain torch.
 FUSED_CONT = True
@@ -61,51 +60,25 @@ _OWN_DEFAULTS = {"architecture": "CONT_MLP", "obs_mode": "obj", "backend": "Synt
                  "vecnorm_reward": False}  # the env's own chain normalises (:99-100)
 # fields of args.Args with no meaning here: the Atari / PPObj / pixel features, the Categorical
 # sampler's noise, DP
-_SKIP = {"patch_size", "author", "test_modifs", "detection_failure_probability",
-         "mislabeling_probability", "noise_std", "extra_planes", "v2", "masked_wrapper",
-         "add_pixels", "rollout_frame_cache", "rollout_fusion", "rollout_cache_ring",
-         "update_frame_dedup", "x6_weight_planes", "emb_dim", "num_heads", "num_blocks",
-         "eval_episodes", "dp_overlap", "dp_exchange", "sampling_noise", "fused_heads_loss",
-         "sample_records_min", "conv_channels_last", "conv_benchmark", "encoder_dims",
-         "decoder_dims", "x6_gemm", "gemm_table", "num_features", "modifs", "new_rf", "frameskip"}
-_FIXED = (("rollout_frame_cache", False), ("rollout_fusion", False), ("rollout_cache_ring", False),
-          ("update_frame_dedup", False), ("x6_weight_planes", False), ("eval_episodes", 0),
-          ("dp_overlap", False), ("dp_exchange", False),
-          ("sampling_noise", "torch"),  # no Exp(1) stream: acting draws are the trainer's randn
-          ("fused_heads_loss", False), ("sample_records_min", -1), ("conv_channels_last", False),
-          ("x6_gemm", False), ("gemm_table", False))  # 64-wide tanh MLPs: torch's GEMMs
+_SKIP = CORE_SKIP | {"sampling_noise", "fused_heads_loss", "sample_records_min",
+                     "conv_channels_last", "conv_benchmark", "encoder_dims", "decoder_dims",
+                     "x6_gemm", "gemm_table", "num_features", "modifs", "new_rf", "frameskip"}
+_FIXED = CORE_FIXED + (
+    ("sampling_noise", "torch"),  # no Exp(1) stream: acting draws are the trainer's randn
+    ("fused_heads_loss", False), ("sample_records_min", -1), ("conv_channels_last", False),
+    ("x6_gemm", False), ("gemm_table", False))  # 64-wide tanh MLPs: torch's GEMMs
 
-
-def _fields():
-    names = {n for n, _, _ in _REFERENCE_FIELDS}
-    out = list(_REFERENCE_FIELDS)
-    for f in dataclasses.fields(Args):
-        if f.name not in names and f.name not in _SKIP:
-            out.append((f.name, f.type, _OWN_DEFAULTS.get(f.name, f.default)))
-    return [(n, t, dataclasses.field(default=d)) for n, t, d in out]
-
-
-ContPPOArgs = dataclasses.make_dataclass("ContPPOArgs", _fields())
-ContPPOArgs.__doc__ = ("The flags of ppo_continuous_action.py:17-83 (same names, order and "
-                       "defaults) + rpo_alpha + this build's additions.")
-for _f in dataclasses.fields(Args):
-    if _f.name in _SKIP:
-        setattr(ContPPOArgs, _f.name, _f.default)
-for _n, _v in _FIXED:
-    setattr(ContPPOArgs, _n, _v)
+ContPPOArgs = learner_args(
+    "ContPPOArgs", "The flags of ppo_continuous_action.py:17-83 (same names, order and "
+                   "defaults) + rpo_alpha + this build's additions.",
+    _REFERENCE_FIELDS, _SKIP, _OWN_DEFAULTS, fixed=_FIXED)
 
 
 def finalize(args, world_size: int = 1):
     """Derived sizes (ppo_continuous_action.py:146-148) and the checks that apply."""
-    if world_size != 1:
-        raise NotImplementedError("the continuous-action PPO learner runs on one GPU")
     if args.rpo_alpha < 0:
         raise ValueError(f"rpo_alpha = {args.rpo_alpha} must not be negative")
-    args.world_size = 1
-    args.local_num_envs = args.num_envs
-    args.batch_size = args.local_batch_size = int(args.num_envs * args.num_steps)
-    args.minibatch_size = args.local_minibatch_size = int(args.batch_size // args.num_minibatches)
-    args.num_iterations = args.total_timesteps // args.batch_size
+    single_gpu_sizes(args, world_size, "the continuous-action PPO learner")
     if args.minibatch_size < 1 or args.batch_size % args.num_minibatches:
         raise ValueError(f"batch size {args.batch_size} must be divisible by num_minibatches="
                          f"{args.num_minibatches}")
@@ -337,20 +310,7 @@ def run_contppo(args, device=None) -> ContPPOTrainer:
 def main(argv=None, defaults: dict | None = None,
          description: str = "oc_cleanrl_amd continuous-action PPO (ppo_continuous_action.py "
                             "surface)"):
-    args = parse_dataclass(ContPPOArgs, argv, defaults, description)
-    _, local_rank, world = env_rank()
-    args = finalize(args, world)
-    device = torch.device(f"cuda:{local_rank}")
-    torch.cuda.set_device(device)
-    tr = None
-    try:
-        tr = run_contppo(args, device)
-        if tr.last_metrics:
-            print({k: round(v, 5) for k, v in tr.last_metrics.items()})
-    finally:
-        if tr is not None:
-            tr.close()
-    return tr
+    return learner_main(ContPPOArgs, finalize, run_contppo, description, argv, defaults)
 
 
 if __name__ == "__main__":

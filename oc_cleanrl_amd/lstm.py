@@ -24,7 +24,6 @@ for a stateful agent; one GPU.
 """
 from __future__ import annotations
 
-import dataclasses
 from types import SimpleNamespace
 from typing import Optional
 
@@ -34,8 +33,9 @@ import torch.nn as nn
 
 from . import ops
 from .agents import EnvSpec, _ActorCritic, fused_trunk, layer_init, linear_act, object_trunk
-from .args import Args, env_rank, parse_dataclass
-from .trainer import PPOTrainer, run
+from .args import (CORE_FIXED, CORE_SKIP, check_sampling_noise, learner_args,
+                   single_gpu_sizes)
+from .trainer import PPOTrainer, learner_main, run
 
 # The fused recurrence (ops.lstm_seq / ops.lstm_step); False: the reference's per-step nn.LSTM loop.
 FUSED_LSTM = True
@@ -60,43 +60,17 @@ _REFERENCE_FIELDS = [
 _OWN_DEFAULTS = {"architecture": "PPO_OBJ", "obs_mode": "obj", "backend": "Synthetic",
                  "vecnorm_reward": False,  # the script clips rewards and has no VecNormalize
                  "encoder_dims": (128, 64), "decoder_dims": (128,)}
-_SKIP = {"patch_size", "author", "test_modifs", "detection_failure_probability",
-         "mislabeling_probability", "noise_std", "extra_planes", "v2", "masked_wrapper",
-         "add_pixels", "rollout_frame_cache", "rollout_fusion", "rollout_cache_ring",
-         "update_frame_dedup", "x6_weight_planes", "emb_dim", "num_heads", "num_blocks",
-         "eval_episodes", "dp_overlap", "dp_exchange"}
+_OWN_FIELDS = [("lstm_hidden", int, 128)]  # nn.LSTM(trunk_out, 128) at :131
 
-
-def _fields():
-    names = {n for n, _, _ in _REFERENCE_FIELDS}
-    out = list(_REFERENCE_FIELDS)
-    for f in dataclasses.fields(Args):
-        if f.name not in names and f.name not in _SKIP:
-            out.append((f.name, f.type, _OWN_DEFAULTS.get(f.name, f.default)))
-    out.append(("lstm_hidden", int, 128))  # nn.LSTM(trunk_out, 128) at :131
-    return [(n, t, dataclasses.field(default=d)) for n, t, d in out]
-
-
-LSTMArgs = dataclasses.make_dataclass("LSTMArgs", _fields())
-LSTMArgs.__doc__ = ("The flags of ppo_atari_lstm.py:27-86 (same names, order and defaults) + this "
-                    "build's additions.")
-# the fields of args.Args left off the command line stay readable (PPOTrainer reads some): Args'
-# own defaults, with the PPObj-only rollout / update features fixed off
-for _f in dataclasses.fields(Args):
-    if _f.name in _SKIP:
-        setattr(LSTMArgs, _f.name, _f.default)
-for _n, _v in (("rollout_frame_cache", False), ("rollout_fusion", False),
-               ("rollout_cache_ring", False), ("update_frame_dedup", False),
-               ("x6_weight_planes", False), ("eval_episodes", 0), ("dp_overlap", False),
-               ("dp_exchange", False)):
-    setattr(LSTMArgs, _n, _v)
+LSTMArgs = learner_args(
+    "LSTMArgs", "The flags of ppo_atari_lstm.py:27-86 (same names, order and defaults) + this "
+                "build's additions.",
+    _REFERENCE_FIELDS, CORE_SKIP, _OWN_DEFAULTS, _OWN_FIELDS, CORE_FIXED)
 
 
 def finalize(args, world_size: int = 1):
     """Derived sizes (ppo_atari_lstm.py:175-177), the script's assertion at :296 and the checks of
     args.finalize that apply."""
-    if world_size != 1:
-        raise NotImplementedError("the LSTM learner runs on one GPU")
     if args.architecture not in ARCHITECTURES:
         raise NotImplementedError(f"architecture must be one of {ARCHITECTURES}")
     if (args.obs_mode == "obj") != (args.architecture == "PPO_OBJ"):
@@ -104,18 +78,12 @@ def finalize(args, world_size: int = 1):
     if args.num_envs % args.num_minibatches:
         raise ValueError(f"num_envs={args.num_envs} must be divisible by num_minibatches="
                          f"{args.num_minibatches}: a minibatch is whole environments")
-    args.world_size = 1
-    args.local_num_envs = args.num_envs
-    args.batch_size = args.local_batch_size = int(args.num_envs * args.num_steps)
-    args.minibatch_size = args.local_minibatch_size = int(args.batch_size // args.num_minibatches)
-    args.num_iterations = args.total_timesteps // args.batch_size
+    single_gpu_sizes(args, world_size, "the LSTM learner")
     if not ops.lstm_shape_ok(args.num_steps, args.num_envs // args.num_minibatches, 1,
                              args.lstm_hidden):
         raise ValueError(f"lstm_hidden={args.lstm_hidden} with num_steps={args.num_steps}: the "
                          f"LSTM kernels take a hidden size in {ops.LSTM_HIDDEN} and >= 1 step")
-    if args.sampling_noise not in ("kernel", "head", "torch", "rollout"):
-        raise ValueError(f"sampling_noise must be kernel, head, torch or rollout, got "
-                         f"{args.sampling_noise!r}")
+    check_sampling_noise(args)
     return args
 
 
@@ -346,21 +314,8 @@ def run_lstm(args, device=None) -> LSTMTrainer:
 
 
 def main(argv=None):
-    args = parse_dataclass(LSTMArgs, argv, None,
-                           "oc_cleanrl_amd recurrent PPO (ppo_atari_lstm.py surface)")
-    _, local_rank, world = env_rank()
-    args = finalize(args, world)
-    device = torch.device(f"cuda:{local_rank}")
-    torch.cuda.set_device(device)
-    tr = None
-    try:
-        tr = run_lstm(args, device)
-        if tr.last_metrics:
-            print({k: round(v, 5) for k, v in tr.last_metrics.items()})
-    finally:
-        if tr is not None:
-            tr.close()
-    return tr
+    return learner_main(LSTMArgs, finalize, run_lstm,
+                        "oc_cleanrl_amd recurrent PPO (ppo_atari_lstm.py surface)", argv)
 
 
 if __name__ == "__main__":

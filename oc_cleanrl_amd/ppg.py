@@ -35,11 +35,6 @@ script's anneal_lr takes its fraction from the in-phase update index (:291); so 
 """
 from __future__ import annotations
 
-import dataclasses
-import json
-import time
-from dataclasses import asdict
-from pathlib import Path
 from typing import Optional
 
 import numpy as np
@@ -48,8 +43,9 @@ import torch.nn as nn
 
 from . import ops
 from .agents import EnvSpec, _ActorCritic, layer_init, object_trunk
-from .args import Args, env_rank, parse_dataclass
-from .trainer import PPOTrainer, _graph_capture, _own_tensors
+from .args import (CORE_FIXED, CORE_SKIP, check_sampling_noise, learner_args,
+                   single_gpu_sizes)
+from .trainer import PPOTrainer, _graph_capture, learner_main, run
 
 # The three PPG pieces (ops.ppg_aux_gather, ops.ppg_aux_loss_fwd_bwd, ops.FlatAdamSegments' step);
 # False: plain torch ops in their place
@@ -80,44 +76,22 @@ _OWN_DEFAULTS = {"architecture": "PPG_OBJ", "obs_mode": "obj", "backend": "Synth
 # fields of args.Args with no meaning here: the PPObj-only rollout / update features, DP, the
 # optimizer switch (aux_critic needs the segmented step), and PPO's epoch count and minibatch
 # advantage normalisation (e_policy and adv_norm_fullbatch stand in their place)
-_SKIP = {"patch_size", "author", "test_modifs", "detection_failure_probability",
-         "mislabeling_probability", "noise_std", "extra_planes", "v2", "masked_wrapper",
-         "add_pixels", "rollout_frame_cache", "rollout_fusion", "rollout_cache_ring",
-         "update_frame_dedup", "x6_weight_planes", "emb_dim", "num_heads", "num_blocks",
-         "eval_episodes", "dp_overlap", "dp_exchange", "fused_heads_loss", "sample_records_min",
-         "conv_channels_last", "fused_optimizer", "update_epochs", "norm_adv"}
-_FIXED = (("rollout_frame_cache", False), ("rollout_fusion", False), ("rollout_cache_ring", False),
-          ("update_frame_dedup", False), ("x6_weight_planes", False), ("eval_episodes", 0),
-          ("dp_overlap", False), ("dp_exchange", False), ("fused_heads_loss", False),
-          ("sample_records_min", -1), ("conv_channels_last", False), ("fused_optimizer", True),
-          ("norm_adv", False))
+_SKIP = CORE_SKIP | {"fused_heads_loss", "sample_records_min", "conv_channels_last",
+                     "fused_optimizer", "update_epochs", "norm_adv"}
+_FIXED = CORE_FIXED + (("fused_heads_loss", False), ("sample_records_min", -1),
+                       ("conv_channels_last", False), ("fused_optimizer", True),
+                       ("norm_adv", False))
 
-
-def _fields():
-    names = {n for n, _, _ in _REFERENCE_FIELDS}
-    out = list(_REFERENCE_FIELDS)
-    for f in dataclasses.fields(Args):
-        if f.name not in names and f.name not in _SKIP:
-            out.append((f.name, f.type, _OWN_DEFAULTS.get(f.name, f.default)))
-    return [(n, t, dataclasses.field(default=d)) for n, t, d in out]
-
-
-PPGArgs = dataclasses.make_dataclass("PPGArgs", _fields())
-PPGArgs.__doc__ = ("The flags of ppg_procgen.py:20-98 (same names, order and defaults) + this "
-                   "build's additions.")
-for _f in dataclasses.fields(Args):
-    if _f.name in _SKIP:
-        setattr(PPGArgs, _f.name, _f.default)
-for _n, _v in _FIXED:
-    setattr(PPGArgs, _n, _v)
+PPGArgs = learner_args(
+    "PPGArgs", "The flags of ppg_procgen.py:20-98 (same names, order and defaults) + this "
+               "build's additions.",
+    _REFERENCE_FIELDS, _SKIP, _OWN_DEFAULTS, fixed=_FIXED)
 
 
 def finalize(args, world_size: int = 1, trainer: bool = True):
     """Derived sizes (ppg_procgen.py:216-221) and the checks of args.finalize that apply.
     trainer: the arguments are for PPGTrainer, which trains PPG_OBJ only (False: for building the
     modules)."""
-    if world_size != 1:
-        raise NotImplementedError(f"world_size = {world_size}: the PPG learner runs on one GPU")
     if args.architecture not in ARCHITECTURES:
         raise NotImplementedError(f"architecture must be one of {ARCHITECTURES}")
     if (args.obs_mode == "obj") != (args.architecture == "PPG_OBJ"):
@@ -130,16 +104,10 @@ def finalize(args, world_size: int = 1, trainer: bool = True):
     if args.n_aux_grad_accum != 1:
         raise NotImplementedError("n_aux_grad_accum != 1: gradient accumulation over auxiliary "
                                   "minibatches is not built (DESIGN 8)")
-    if args.sampling_noise not in ("kernel", "head", "torch", "rollout"):
-        raise ValueError(f"sampling_noise must be kernel, head, torch or rollout, got "
-                         f"{args.sampling_noise!r}")
+    check_sampling_noise(args)
     if min(args.n_iteration, args.e_policy, args.e_auxiliary, args.num_aux_rollouts) < 1:
         raise ValueError("n_iteration, e_policy, e_auxiliary and num_aux_rollouts must be >= 1")
-    args.world_size = 1
-    args.local_num_envs = args.num_envs
-    args.batch_size = args.local_batch_size = int(args.num_envs * args.num_steps)
-    args.minibatch_size = args.local_minibatch_size = int(args.batch_size // args.num_minibatches)
-    args.num_iterations = args.total_timesteps // args.batch_size
+    single_gpu_sizes(args, world_size, "the PPG learner")
     args.num_phases = int(args.num_iterations // args.n_iteration)
     args.aux_batch_rollouts = int(args.num_envs * args.n_iteration)
     args.update_epochs = args.e_policy  # PPOTrainer's name for the policy epochs
@@ -492,6 +460,10 @@ class PPGTrainer(PPOTrainer):
         return self.aux_metrics
 
     # ---- iteration / metrics -----------------------------------------------------------------
+    def run_iterations(self) -> int:
+        """Whole phases only (ppg_procgen.py:285-288): num_phases of n_iteration iterations."""
+        return self.args.num_phases * self.args.n_iteration
+
     def train_iteration(self, collect_metrics: bool = True, lag: bool = False) -> dict:
         """One policy iteration; the phase's last one is followed by the auxiliary phase."""
         a = self.args
@@ -566,49 +538,13 @@ def aux_losses_torch(logits, value, aux_value, old_logits, returns):
 
 def run_ppg(args, device=None) -> PPGTrainer:
     """The script body: num_phases phases of n_iteration policy iterations and an auxiliary
-    phase each, SPS, metrics JSONL, checkpoints."""
-    if device is None:
-        device = torch.device("cuda:0")
-    tr = PPGTrainer(args, device)
-    run_name = f"{args.env_id}__{args.exp_name}__{args.seed}__{int(time.time())}".replace("/", "_")
-    run_dir = Path(args.log_dir) / run_name
-    run_dir.mkdir(parents=True, exist_ok=True)
-    (run_dir / "args.json").write_text(json.dumps(asdict(args), indent=1, default=str))
-    start, it = time.time(), 0
-    with open(run_dir / "metrics.jsonl", "w") as writer:
-        for _ in range(args.num_phases):
-            for _ in range(args.n_iteration):
-                it += 1
-                if it % args.checkpoint_interval == 0 and args.save_model:
-                    tr.save(run_dir / f"{args.exp_name}_{it}.cleanrl_model")
-                collect = it % args.metrics_every == 0 or it == args.num_phases * args.n_iteration
-                m = tr.train_iteration(collect_metrics=collect)
-                if m:
-                    m["charts/SPS"] = int(tr.global_step / (time.time() - start))
-                    m["global_step"] = tr.global_step
-                    writer.write(json.dumps(m) + "\n")
-                    writer.flush()
-    if args.save_model:
-        torch.save({"model_weights": _own_tensors(tr.agent.state_dict()), "args": asdict(args)},
-                   run_dir / f"{args.exp_name}_final.cleanrl_model")
-    return tr
+    phase each (PPGTrainer.run_iterations / train_iteration), SPS, metrics JSONL, checkpoints."""
+    return run(args, device, trainer_cls=PPGTrainer)
 
 
 def main(argv=None):
-    args = parse_dataclass(PPGArgs, argv, None, "oc_cleanrl_amd PPG (ppg_procgen.py surface)")
-    _, local_rank, world = env_rank()
-    args = finalize(args, world)
-    device = torch.device(f"cuda:{local_rank}")
-    torch.cuda.set_device(device)
-    tr = None
-    try:
-        tr = run_ppg(args, device)
-        if tr.last_metrics:
-            print({k: round(v, 5) for k, v in tr.last_metrics.items()})
-    finally:
-        if tr is not None:
-            tr.close()
-    return tr
+    return learner_main(PPGArgs, finalize, run_ppg,
+                        "oc_cleanrl_amd PPG (ppg_procgen.py surface)", argv)
 
 
 if __name__ == "__main__":

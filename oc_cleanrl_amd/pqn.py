@@ -26,7 +26,6 @@ counter-based stream), not torch.rand per env; one GPU.
 """
 from __future__ import annotations
 
-import dataclasses
 from typing import Optional
 
 import numpy as np
@@ -36,8 +35,8 @@ import torch.nn.functional as F
 
 from . import ops
 from .agents import EnvSpec, Predictor, layer_init, linear_act, object_trunk
-from .args import Args, env_rank, parse_dataclass
-from .trainer import PPOTrainer, run
+from .args import CORE_FIXED, CORE_SKIP, learner_args, single_gpu_sizes
+from .trainer import PPOTrainer, learner_main, run
 
 # The fused kernels (ops.ln_relu, ops.pqn_act, ops.pqn_loss_fwd_bwd, ops.FlatRAdam); False:
 # torch's layer_norm / relu, argmax, mse_loss and optim.RAdam.
@@ -52,7 +51,7 @@ FUSED_LN_UPDATE = False
 ARCHITECTURES = ("PQN_OBJ", "PQN")
 
 # pqn_atari_envpool.py:17-73, same names, order and defaults
-_REFERENCE_FIELDS = [
+REFERENCE_FIELDS = [
     ("exp_name", str, "pqn_atari_envpool"), ("seed", int, 1), ("torch_deterministic", bool, True),
     ("cuda", bool, True), ("track", bool, False), ("wandb_project_name", str, "cleanRL"),
     ("wandb_entity", Optional[str], None), ("capture_video", bool, False),
@@ -65,59 +64,32 @@ _REFERENCE_FIELDS = [
 ]
 # [oc_cleanrl_amd] additions: what PPOTrainer reads beyond the script's flags (args.Args' own
 # defaults unless listed), the network choice and the observation geometry
-_OWN_DEFAULTS = {"architecture": "PQN_OBJ", "obs_mode": "obj", "backend": "Synthetic",
-                 "vecnorm_reward": False,  # the script clips rewards and has no VecNormalize
-                 "encoder_dims": (128, 64), "decoder_dims": (128,)}
+OWN_DEFAULTS = {"architecture": "PQN_OBJ", "obs_mode": "obj", "backend": "Synthetic",
+                "vecnorm_reward": False,  # the script clips rewards and has no VecNormalize
+                "encoder_dims": (128, 64), "decoder_dims": (128,)}
 # fields of args.Args with no meaning here: PPO's loss, the PPObj-only rollout / update features
 # (a LayerNorm sits inside every layer those kernels fuse), the sampler's noise, DP
-_SKIP = {"patch_size", "author", "test_modifs", "detection_failure_probability",
-         "mislabeling_probability", "noise_std", "extra_planes", "v2", "masked_wrapper",
-         "add_pixels", "rollout_frame_cache", "rollout_fusion", "rollout_cache_ring",
-         "update_frame_dedup", "x6_weight_planes", "emb_dim", "num_heads", "num_blocks",
-         "eval_episodes", "dp_overlap", "dp_exchange", "gae_lambda", "norm_adv", "clip_coef",
-         "clip_vloss", "ent_coef", "vf_coef", "target_kl", "sampling_noise", "fused_heads_loss",
-         "sample_records_min", "conv_channels_last"}
-_FIXED = (("rollout_frame_cache", False), ("rollout_fusion", False), ("rollout_cache_ring", False),
-          ("update_frame_dedup", False), ("x6_weight_planes", False), ("eval_episodes", 0),
-          ("dp_overlap", False), ("dp_exchange", False), ("norm_adv", False), ("target_kl", None),
-          ("sampling_noise", "torch"),  # no Exp(1) stream: acting draws from ocppo_epsilon_greedy's
-          ("fused_heads_loss", False), ("sample_records_min", -1), ("conv_channels_last", False))
+SKIP = CORE_SKIP | {"gae_lambda", "norm_adv", "clip_coef", "clip_vloss", "ent_coef", "vf_coef",
+                    "target_kl", "sampling_noise", "fused_heads_loss", "sample_records_min",
+                    "conv_channels_last"}
+FIXED = CORE_FIXED + (
+    ("norm_adv", False), ("target_kl", None),
+    ("sampling_noise", "torch"),  # no Exp(1) stream: acting draws from ocppo_epsilon_greedy's
+    ("fused_heads_loss", False), ("sample_records_min", -1), ("conv_channels_last", False))
 
-
-def _fields():
-    names = {n for n, _, _ in _REFERENCE_FIELDS}
-    out = list(_REFERENCE_FIELDS)
-    for f in dataclasses.fields(Args):
-        if f.name not in names and f.name not in _SKIP:
-            out.append((f.name, f.type, _OWN_DEFAULTS.get(f.name, f.default)))
-    return [(n, t, dataclasses.field(default=d)) for n, t, d in out]
-
-
-PQNArgs = dataclasses.make_dataclass("PQNArgs", _fields())
-PQNArgs.__doc__ = ("The flags of pqn_atari_envpool.py:17-73 (same names, order and defaults) + "
-                   "this build's additions.")
-# the fields of args.Args left off the command line stay readable (PPOTrainer reads some): Args'
-# own defaults, with the PPO-only features fixed off
-for _f in dataclasses.fields(Args):
-    if _f.name in _SKIP:
-        setattr(PQNArgs, _f.name, _f.default)
-for _n, _v in _FIXED:
-    setattr(PQNArgs, _n, _v)
+PQNArgs = learner_args(
+    "PQNArgs", "The flags of pqn_atari_envpool.py:17-73 (same names, order and defaults) + "
+               "this build's additions.",
+    REFERENCE_FIELDS, SKIP, OWN_DEFAULTS, fixed=FIXED)
 
 
 def finalize(args, world_size: int = 1):
     """Derived sizes (pqn_atari_envpool.py:148-150) and the checks of args.finalize that apply."""
-    if world_size != 1:
-        raise NotImplementedError("the PQN learner runs on one GPU")
     if args.architecture not in ARCHITECTURES:
         raise NotImplementedError(f"architecture must be one of {ARCHITECTURES}")
     if (args.obs_mode == "obj") != (args.architecture == "PQN_OBJ"):
         raise ValueError('architecture PQN_OBJ reads --obs_mode obj, PQN reads pixels (dqn)')
-    args.world_size = 1
-    args.local_num_envs = args.num_envs
-    args.batch_size = args.local_batch_size = int(args.num_envs * args.num_steps)
-    args.minibatch_size = args.local_minibatch_size = int(args.batch_size // args.num_minibatches)
-    args.num_iterations = args.total_timesteps // args.batch_size
+    single_gpu_sizes(args, world_size, "the PQN learner")
     if args.minibatch_size < 1 or args.batch_size % args.num_minibatches:
         raise ValueError(f"batch size {args.batch_size} must be divisible by num_minibatches="
                          f"{args.num_minibatches}")
@@ -353,20 +325,8 @@ def run_pqn(args, device=None) -> PQNTrainer:
 
 
 def main(argv=None):
-    args = parse_dataclass(PQNArgs, argv, None, "oc_cleanrl_amd PQN (pqn_atari_envpool.py surface)")
-    _, local_rank, world = env_rank()
-    args = finalize(args, world)
-    device = torch.device(f"cuda:{local_rank}")
-    torch.cuda.set_device(device)
-    tr = None
-    try:
-        tr = run_pqn(args, device)
-        if tr.last_metrics:
-            print({k: round(v, 5) for k, v in tr.last_metrics.items()})
-    finally:
-        if tr is not None:
-            tr.close()
-    return tr
+    return learner_main(PQNArgs, finalize, run_pqn,
+                        "oc_cleanrl_amd PQN (pqn_atari_envpool.py surface)", argv)
 
 
 if __name__ == "__main__":

@@ -35,8 +35,6 @@ torch; exploration is ocppo_epsilon_greedy's law; one GPU; a single LSTM layer).
 """
 from __future__ import annotations
 
-import dataclasses
-
 import torch
 import torch.nn as nn
 
@@ -44,10 +42,10 @@ from . import lstm as lstm_mod
 from . import ops
 from . import pqn as pqn_mod
 from .agents import EnvSpec, Predictor, layer_init
-from .args import Args, env_rank, parse_dataclass
+from .args import learner_args, single_gpu_sizes
 from .lstm import LSTMTrainer, Recurrence, epoch_indices, init_lstm  # noqa: F401  (re-exported)
 from .pqn import PQNTrainer, linear_schedule  # noqa: F401  (re-exported)
-from .trainer import run
+from .trainer import learner_main, run
 
 # This module's two fused calls (ops.pqn_lstm_act, ops.pqn_head_loss_fwd_bwd); False: the
 # composition of the parents' kernels.
@@ -62,38 +60,20 @@ ARCHITECTURES = ("PQN_LSTM_OBJ", "PQN_LSTM")
 # pqn_atari_envpool_lstm.py:20-74: pqn_atari_envpool.py's fields, names and order, with the
 # script's own name and its gradient clip
 _REFERENCE_DEFAULTS = {"exp_name": "pqn_atari_envpool_lstm", "max_grad_norm": 0.5}
-_REFERENCE_FIELDS = [(n, t, _REFERENCE_DEFAULTS.get(n, d)) for n, t, d in pqn_mod._REFERENCE_FIELDS]
+_REFERENCE_FIELDS = [(n, t, _REFERENCE_DEFAULTS.get(n, d)) for n, t, d in pqn_mod.REFERENCE_FIELDS]
 # [oc_cleanrl_amd] additions, as pqn.py's, and the LSTM width
-_OWN_DEFAULTS = dict(pqn_mod._OWN_DEFAULTS, architecture="PQN_LSTM_OBJ")
-_SKIP = pqn_mod._SKIP
-_FIXED = pqn_mod._FIXED
+_OWN_DEFAULTS = dict(pqn_mod.OWN_DEFAULTS, architecture="PQN_LSTM_OBJ")
+_OWN_FIELDS = [("lstm_hidden", int, 128)]  # nn.LSTM(512, 128) at :135
 
-
-def _fields():
-    names = {n for n, _, _ in _REFERENCE_FIELDS}
-    out = list(_REFERENCE_FIELDS)
-    for f in dataclasses.fields(Args):
-        if f.name not in names and f.name not in _SKIP:
-            out.append((f.name, f.type, _OWN_DEFAULTS.get(f.name, f.default)))
-    out.append(("lstm_hidden", int, 128))  # nn.LSTM(512, 128) at :135
-    return [(n, t, dataclasses.field(default=d)) for n, t, d in out]
-
-
-PQNLSTMArgs = dataclasses.make_dataclass("PQNLSTMArgs", _fields())
-PQNLSTMArgs.__doc__ = ("The flags of pqn_atari_envpool_lstm.py:20-74 (same names, order and "
-                       "defaults) + this build's additions.")
-for _f in dataclasses.fields(Args):
-    if _f.name in _SKIP:
-        setattr(PQNLSTMArgs, _f.name, _f.default)
-for _n, _v in _FIXED:
-    setattr(PQNLSTMArgs, _n, _v)
+PQNLSTMArgs = learner_args(
+    "PQNLSTMArgs", "The flags of pqn_atari_envpool_lstm.py:20-74 (same names, order and "
+                   "defaults) + this build's additions.",
+    _REFERENCE_FIELDS, pqn_mod.SKIP, _OWN_DEFAULTS, _OWN_FIELDS, pqn_mod.FIXED)
 
 
 def finalize(args, world_size: int = 1):
     """Derived sizes (pqn_atari_envpool_lstm.py:175-177), the script's assertion at :304 and the
     checks of pqn.finalize / lstm.finalize that apply."""
-    if world_size != 1:
-        raise NotImplementedError("the recurrent PQN learner runs on one GPU")
     if args.architecture not in ARCHITECTURES:
         raise NotImplementedError(f"architecture must be one of {ARCHITECTURES}")
     if (args.obs_mode == "obj") != (args.architecture == "PQN_LSTM_OBJ"):
@@ -102,11 +82,7 @@ def finalize(args, world_size: int = 1):
     if args.num_minibatches < 1 or args.num_envs % args.num_minibatches:
         raise ValueError(f"num_envs={args.num_envs} must be divisible by num_minibatches="
                          f"{args.num_minibatches}: a minibatch is whole environments")
-    args.world_size = 1
-    args.local_num_envs = args.num_envs
-    args.batch_size = args.local_batch_size = int(args.num_envs * args.num_steps)
-    args.minibatch_size = args.local_minibatch_size = int(args.batch_size // args.num_minibatches)
-    args.num_iterations = args.total_timesteps // args.batch_size
+    single_gpu_sizes(args, world_size, "the recurrent PQN learner")
     if not ops.lstm_shape_ok(args.num_steps, args.num_envs // args.num_minibatches, 1,
                              args.lstm_hidden):
         raise ValueError(f"lstm_hidden={args.lstm_hidden} with num_steps={args.num_steps}: the "
@@ -263,21 +239,8 @@ def run_pqn_lstm(args, device=None) -> PQNLSTMTrainer:
 
 
 def main(argv=None):
-    args = parse_dataclass(PQNLSTMArgs, argv, None,
-                           "oc_cleanrl_amd recurrent PQN (pqn_atari_envpool_lstm.py surface)")
-    _, local_rank, world = env_rank()
-    args = finalize(args, world)
-    device = torch.device(f"cuda:{local_rank}")
-    torch.cuda.set_device(device)
-    tr = None
-    try:
-        tr = run_pqn_lstm(args, device)
-        if tr.last_metrics:
-            print({k: round(v, 5) for k, v in tr.last_metrics.items()})
-    finally:
-        if tr is not None:
-            tr.close()
-    return tr
+    return learner_main(PQNLSTMArgs, finalize, run_pqn_lstm,
+                        "oc_cleanrl_amd recurrent PQN (pqn_atari_envpool_lstm.py surface)", argv)
 
 
 if __name__ == "__main__":

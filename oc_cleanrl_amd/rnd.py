@@ -35,7 +35,6 @@ f64 (numpy's are f32); one GPU.
 """
 from __future__ import annotations
 
-import dataclasses
 from typing import Optional
 
 import numpy as np
@@ -45,8 +44,9 @@ import torch.nn.functional as F
 
 from . import agents, ops
 from .agents import EnvSpec, _ActorCritic, layer_init, linear_act, object_trunk
-from .args import Args, env_rank, parse_dataclass
-from .trainer import PPOTrainer, _own_tensors, run
+from .args import (CORE_FIXED, CORE_SKIP, check_sampling_noise, learner_args,
+                   parse_dataclass, single_gpu_sizes)  # noqa: F401  (parse_dataclass: re-exported)
+from .trainer import PPOTrainer, _own_tensors, learner_main, run
 
 # The six RND kernels (ops.rms_update, rnd_normalize, rnd_curiosity, rnd_reward_norm, rnd_gae,
 # rnd_aux_loss_fwd_bwd); False: plain torch ops in their place
@@ -78,44 +78,21 @@ _OWN_DEFAULTS = {"architecture": "RND_OBJ", "obs_mode": "obj", "backend": "Synth
 # fields of args.Args with no meaning here: the PPObj-only rollout / update features (the
 # curiosity step needs the stored next observation between two steps; the heads are not one
 # Linear each), DP, and the optimizer switch (the flat buffers hold two modules' parameters)
-_SKIP = {"patch_size", "author", "test_modifs", "detection_failure_probability",
-         "mislabeling_probability", "noise_std", "extra_planes", "v2", "masked_wrapper",
-         "add_pixels", "rollout_frame_cache", "rollout_fusion", "rollout_cache_ring",
-         "update_frame_dedup", "x6_weight_planes", "emb_dim", "num_heads", "num_blocks",
-         "eval_episodes", "dp_overlap", "dp_exchange", "fused_heads_loss", "sample_records_min",
-         "conv_channels_last", "fused_optimizer"}
-_FIXED = (("rollout_frame_cache", False), ("rollout_fusion", False), ("rollout_cache_ring", False),
-          ("update_frame_dedup", False), ("x6_weight_planes", False), ("eval_episodes", 0),
-          ("dp_overlap", False), ("dp_exchange", False), ("fused_heads_loss", False),
-          ("sample_records_min", -1), ("conv_channels_last", False), ("fused_optimizer", True))
+_SKIP = CORE_SKIP | {"fused_heads_loss", "sample_records_min", "conv_channels_last",
+                     "fused_optimizer"}
+_FIXED = CORE_FIXED + (("fused_heads_loss", False), ("sample_records_min", -1),
+                       ("conv_channels_last", False), ("fused_optimizer", True))
 
-
-def _fields():
-    names = {n for n, _, _ in _REFERENCE_FIELDS}
-    out = list(_REFERENCE_FIELDS)
-    for f in dataclasses.fields(Args):
-        if f.name not in names and f.name not in _SKIP:
-            out.append((f.name, f.type, _OWN_DEFAULTS.get(f.name, f.default)))
-    out += _OWN_FIELDS
-    return [(n, t, dataclasses.field(default=d)) for n, t, d in out]
-
-
-RNDArgs = dataclasses.make_dataclass("RNDArgs", _fields())
-RNDArgs.__doc__ = ("The flags of ppo_rnd_envpool.py:22-94 (same names, order and defaults) + "
-                   "this build's additions.")
-for _f in dataclasses.fields(Args):
-    if _f.name in _SKIP:
-        setattr(RNDArgs, _f.name, _f.default)
-for _n, _v in _FIXED:
-    setattr(RNDArgs, _n, _v)
+RNDArgs = learner_args(
+    "RNDArgs", "The flags of ppo_rnd_envpool.py:22-94 (same names, order and defaults) + "
+               "this build's additions.",
+    _REFERENCE_FIELDS, _SKIP, _OWN_DEFAULTS, _OWN_FIELDS, _FIXED)
 
 
 def finalize(args, world_size: int = 1, trainer: bool = True):
     """Derived sizes (ppo_rnd_envpool.py:247-249) and the checks of args.finalize that apply.
     trainer: the arguments are for RNDTrainer, which trains RND_OBJ only (False: for building
     the modules)."""
-    if world_size != 1:
-        raise NotImplementedError("the RND learner runs on one GPU")
     if args.architecture not in ARCHITECTURES:
         raise NotImplementedError(f"architecture must be one of {ARCHITECTURES}")
     if (args.obs_mode == "obj") != (args.architecture == "RND_OBJ"):
@@ -127,14 +104,8 @@ def finalize(args, world_size: int = 1, trainer: bool = True):
         raise ValueError(f"update_proportion {args.update_proportion} outside [0, 1]")
     if args.num_iterations_obs_norm_init < 0:
         raise ValueError("num_iterations_obs_norm_init must be >= 0")
-    if args.sampling_noise not in ("kernel", "head", "torch", "rollout"):
-        raise ValueError(f"sampling_noise must be kernel, head, torch or rollout, got "
-                         f"{args.sampling_noise!r}")
-    args.world_size = 1
-    args.local_num_envs = args.num_envs
-    args.batch_size = args.local_batch_size = int(args.num_envs * args.num_steps)
-    args.minibatch_size = args.local_minibatch_size = int(args.batch_size // args.num_minibatches)
-    args.num_iterations = args.total_timesteps // args.batch_size
+    check_sampling_noise(args)
+    single_gpu_sizes(args, world_size, "the RND learner")
     if args.minibatch_size < 1 or args.batch_size % args.num_minibatches:
         raise ValueError(f"batch size {args.batch_size} must be divisible by num_minibatches="
                          f"{args.num_minibatches}")
@@ -549,21 +520,8 @@ def run_rnd(args, device=None) -> RNDTrainer:
 
 
 def main(argv=None):
-    args = parse_dataclass(RNDArgs, argv, None,
-                           "oc_cleanrl_amd RND (ppo_rnd_envpool.py surface)")
-    _, local_rank, world = env_rank()
-    args = finalize(args, world)
-    device = torch.device(f"cuda:{local_rank}")
-    torch.cuda.set_device(device)
-    tr = None
-    try:
-        tr = run_rnd(args, device)
-        if tr.last_metrics:
-            print({k: round(v, 5) for k, v in tr.last_metrics.items()})
-    finally:
-        if tr is not None:
-            tr.close()
-    return tr
+    return learner_main(RNDArgs, finalize, run_rnd,
+                        "oc_cleanrl_amd RND (ppo_rnd_envpool.py surface)", argv)
 
 
 if __name__ == "__main__":

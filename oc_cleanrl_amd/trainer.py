@@ -35,7 +35,7 @@ import torch.nn as nn
 from . import agents, frames, gemm_table, ops, rccl
 from .rccl import RcclComm, RcclExchange
 from .agents import NormalizeImg, PPObj, fused_trunk, linear_relu, make_agent
-from .args import Args
+from .args import Args, env_rank, parse_dataclass
 from .envs import HostVecEnv, make_device_env
 
 
@@ -1149,6 +1149,10 @@ class PPOTrainer:
                     break
 
     # ------------------------------------------------------------------------------------------
+    def run_iterations(self) -> int:
+        """How many train_iteration calls run() makes."""
+        return self.args.num_iterations
+
     def train_iteration(self, collect_metrics: bool = True, lag: bool = False) -> dict:
         """One PPO iteration (:469-670). lag: the iteration's metric scalars are gathered on the
         device and copied to pinned host memory behind its work, and the PREVIOUS iteration's
@@ -1372,13 +1376,14 @@ def run(args: Args, device=None, rank: int = 0, world_size: int = 1,
                                                            f"/tmp/ocppo_watch_{port}"),
                           stall_s=args.stall_timeout,
                           on_fire=lambda rec: print(json.dumps(rec), file=sys.stderr, flush=True))
+    last = tr.run_iterations()
     start = time.time()
-    for it in range(1, args.num_iterations + 1):
+    for it in range(1, last + 1):
         if watch is not None:  # the first two iterations also capture the graphs
             watch.phase(f"iteration {it}", stall_s=args.stall_timeout * (3 if it <= 2 else 1))
         if it % args.checkpoint_interval == 0 and rank == 0 and args.save_model:
             tr.save(run_dir / f"{args.exp_name}_{it}.cleanrl_model")
-        collect = (it % args.metrics_every == 0) or it == args.num_iterations
+        collect = (it % args.metrics_every == 0) or it == last
         m = tr.train_iteration(collect_metrics=collect)
         if writer and m:
             m["charts/SPS"] = int(tr.global_step / (time.time() - start))
@@ -1405,4 +1410,25 @@ def run(args: Args, device=None, rank: int = 0, world_size: int = 1,
         writer.close()
     if watch is not None:
         watch.stop()
+    return tr
+
+
+def learner_main(args_cls, finalize, run_fn, description: str, argv=None,
+                 defaults: dict | None = None) -> PPOTrainer:
+    """`python -m oc_cleanrl_amd.<learner>` of a single-GPU learner on PPOTrainer: the command
+    line over `args_cls`, the module's `finalize` and `run_fn(args, device)` on this rank's
+    device, the last metrics printed, the trainer closed."""
+    args = parse_dataclass(args_cls, argv, defaults, description)
+    _, local_rank, world = env_rank()
+    args = finalize(args, world)
+    device = torch.device(f"cuda:{local_rank}")
+    torch.cuda.set_device(device)
+    tr = None
+    try:
+        tr = run_fn(args, device)
+        if tr.last_metrics:
+            print({k: round(v, 5) for k, v in tr.last_metrics.items()})
+    finally:
+        if tr is not None:
+            tr.close()
     return tr

@@ -35,7 +35,6 @@ delivering whole object sets (OCAtari's OCWrapper) are out of scope.
 """
 from __future__ import annotations
 
-import dataclasses
 from types import SimpleNamespace
 from typing import Optional
 
@@ -45,8 +44,8 @@ from torch.nn import TransformerEncoder, TransformerEncoderLayer
 
 from . import ops
 from .agents import EnvSpec, _ActorCritic, layer_init, linear_act
-from .args import Args, env_rank, parse_dataclass
-from .trainer import PPOTrainer, run
+from .args import CORE_FIXED, CORE_SKIP, learner_args, single_gpu_sizes
+from .trainer import PPOTrainer, learner_main, run
 
 # The fused block path (ops.mha / ops.add_layernorm); False: torch's layer modules everywhere.
 FUSED_ATTN = True
@@ -86,53 +85,33 @@ _REFERENCE_FIELDS = [
 # defaults), the observation geometry, and num_obj
 _OWN_DEFAULTS = {"buffer_window_size": 8,  # S: objects per observation
                  "num_features": 8}        # F: features per object
-_SKIP = {"architecture", "encoder_dims", "decoder_dims", "patch_size", "author", "test_modifs",
-         "detection_failure_probability", "mislabeling_probability", "noise_std", "extra_planes",
-         "v2", "masked_wrapper", "add_pixels", "rollout_frame_cache", "rollout_fusion",
-         "rollout_cache_ring", "update_frame_dedup", "x6_weight_planes"}
-
-
-def _fields():
-    names = {n for n, _, _ in _REFERENCE_FIELDS}
-    out = list(_REFERENCE_FIELDS)
-    for f in dataclasses.fields(Args):
-        if f.name not in names and f.name not in _SKIP:
-            out.append((f.name, f.type, _OWN_DEFAULTS.get(f.name, f.default)))
-    out.append(("num_obj", int, 3))  # leading object-type columns (envs.get_attr("num_obj"))
+_OWN_FIELDS = [
+    ("num_obj", int, 3),  # leading object-type columns (envs.get_attr("num_obj"))
     # dropout > 0 on the fused block path with counter-based masks (off: torch's layer modules)
-    out.append(("fused_dropout", bool, False))
-    return [(n, t, dataclasses.field(default=d)) for n, t, d in out]
+    ("fused_dropout", bool, False)]
+# Where this learner differs from args.CORE_SKIP / CORE_FIXED: the transformer's sizes are the
+# script's flags, the final evaluation and the DP switches stay on its command line, and the
+# network choice is fixed instead
+_ON_THE_COMMAND_LINE = {"emb_dim", "num_heads", "num_blocks", "eval_episodes", "dp_overlap",
+                        "dp_exchange"}
+_SKIP = CORE_SKIP - _ON_THE_COMMAND_LINE | {"architecture", "encoder_dims", "decoder_dims"}
+_FIXED = tuple((n, v) for n, v in CORE_FIXED if n not in _ON_THE_COMMAND_LINE) + (
+    ("encoder_dims", ()), ("decoder_dims", ()), ("architecture", "OC_TRANSFORMER"))
 
-
-TransformerArgs = dataclasses.make_dataclass("TransformerArgs", _fields())
-TransformerArgs.__doc__ = ("The flags of ppo_atari_oc_transformer.py:55-160 (same names and "
-                           "defaults) + this build's additions.")
-# the fields of args.Args left off the command line stay readable (PPOTrainer and its helpers read
-# some): Args' own defaults, with the PPObj-only rollout / update features fixed off
-for _f in dataclasses.fields(Args):
-    if _f.name in _SKIP:
-        setattr(TransformerArgs, _f.name, _f.default)
-for _n, _v in (("rollout_frame_cache", False), ("rollout_fusion", False),
-               ("rollout_cache_ring", False), ("update_frame_dedup", False),
-               ("x6_weight_planes", False), ("encoder_dims", ()), ("decoder_dims", ()),
-               ("architecture", "OC_TRANSFORMER")):
-    setattr(TransformerArgs, _n, _v)
+TransformerArgs = learner_args(
+    "TransformerArgs", "The flags of ppo_atari_oc_transformer.py:55-160 (same names and "
+                       "defaults) + this build's additions.",
+    _REFERENCE_FIELDS, _SKIP, _OWN_DEFAULTS, _OWN_FIELDS, _FIXED)
 
 
 def finalize(args, world_size: int = 1):
     """Derived sizes (ppo_atari_oc_transformer.py:282-284) + the checks of args.finalize that
     apply."""
-    if world_size != 1:
-        raise NotImplementedError("the transformer learner runs on one GPU")
     if args.pooling_type not in POOLING_TYPES:
         raise NotImplementedError(f"pooling_type must be one of {POOLING_TYPES}")
     if args.obs_mode != "obj":
         raise ValueError('the transformer agent reads object sets: --obs_mode obj')
-    args.world_size = 1
-    args.local_num_envs = args.num_envs
-    args.batch_size = args.local_batch_size = int(args.num_envs * args.num_steps)
-    args.minibatch_size = args.local_minibatch_size = int(args.batch_size // args.num_minibatches)
-    args.num_iterations = args.total_timesteps // args.batch_size
+    single_gpu_sizes(args, world_size, "the transformer learner")
     if args.batch_size % args.num_minibatches:
         raise ValueError("batch size must be divisible by num_minibatches")
     if not 1 <= args.num_obj <= args.num_features:
@@ -296,21 +275,9 @@ def run_transformer(args, device=None) -> TransformerTrainer:
 
 
 def main(argv=None):
-    args = parse_dataclass(TransformerArgs, argv, None,
-                           "oc_cleanrl_amd transformer PPO (ppo_atari_oc_transformer.py surface)")
-    _, local_rank, world = env_rank()
-    args = finalize(args, world)
-    device = torch.device(f"cuda:{local_rank}")
-    torch.cuda.set_device(device)
-    tr = None
-    try:
-        tr = run_transformer(args, device)
-        if tr.last_metrics:
-            print({k: round(v, 5) for k, v in tr.last_metrics.items()})
-    finally:
-        if tr is not None:
-            tr.close()
-    return tr
+    return learner_main(TransformerArgs, finalize, run_transformer,
+                        "oc_cleanrl_amd transformer PPO (ppo_atari_oc_transformer.py surface)",
+                        argv)
 
 
 if __name__ == "__main__":
