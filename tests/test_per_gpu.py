@@ -122,14 +122,15 @@ def test_sample_with_given_upperbounds_matches_reference(dev, name):
     assert int(rb.counter) == 2
 
 
-def filled(dev, capacity, n_adds, seed, n_step=1, obs_shape=(4,)):
-    """(device buffer, oracle) after the same `n_adds` random adds."""
+def filled(dev, capacity, n_adds, seed, n_step=1, obs_shape=(4,), done_at=()):
+    """(device buffer, oracle) after the same `n_adds` random adds (those of `done_at` done)."""
     rng = np.random.default_rng(seed)
     rb = make(dev, capacity, obs_shape, n_step=n_step, seed=seed)
     orc = PerOracle(capacity, obs_shape, n_step, 0.99, 0.5)
     obs = rng.integers(0, 256, (n_adds + 1,) + obs_shape).astype(np.uint8)
     rew = rng.choice(np.array([-1, 0, 0, 1, 0.5], f32), n_adds)
     done = rng.random(n_adds) < 0.05
+    done[list(done_at)] = True
     act = rng.integers(0, 6, n_adds)
     for t in range(n_adds):
         dev_add(rb, obs[t], act[t], rew[t], obs[t + 1], done[t])
@@ -205,6 +206,25 @@ def test_capacity_one_million(dev):
     assert set(depth) == {19, 20}
     for B in (32, 1024):
         check_sample(rb, orc, B)
+
+
+def test_add_rows_past_the_grid_cap(dev):
+    """per_add_kernel's grid is capped at 64 workgroups of 256 threads: past D = 16,384 a thread
+    copies more than one element of the row (here up to two, the last round 259 threads wide)
+    before the last arriver writes the tree. The pixel default, 4 x 84 x 84, is past the cap.
+    A done as the newest ring entry (add 5) and one in the middle of the window (add 7, emitted
+    by add 8: the next observation comes from the ring, not from the arguments); eight rows
+    emitted, so pos wraps to 0."""
+    C, D = 8, 16384 + 256 + 3
+    rb, orc, _ = filled(dev, C, 14, seed=11, n_step=3, obs_shape=(D,), done_at=(5, 7))
+    d = download(rb)
+    assert (d["pos"], d["size"]) == (orc.pos, orc.size) == (0, C)
+    assert orc.dones.sum() >= 2 and not orc.dones.all()
+    for key in ("obs", "next_obs", "actions", "rewards", "dones"):
+        assert np.array_equal(d[key], getattr(orc, key)), key  # bitwise
+    assert len({bytes(r) for r in d["obs"]}) == C  # eight different rows
+    assert np.array_equal(d["tree"], orc.tree)  # max_priority is 1: exactly 1 per leaf
+    check_sample(rb, orc, 8)
 
 
 def test_add_sample_update_replay_from_one_graph(dev):
