@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCPPO_ABI_VERSION 42
+#define OCPPO_ABI_VERSION 43
 
 /* status codes */
 #define OCPPO_OK 0
@@ -1788,6 +1788,83 @@ OCPPO_API int ocppo_td3_policy_actions_bwd(ocppo_stream_t stream, const float* d
                                            const float* action_scale, float* dmu);
 OCPPO_API int ocppo_polyak(ocppo_stream_t stream, int n_pairs, const float* const* params,
                            float* const* targets, const int64_t* numels, double tau);
+
+/* ---------------------------------------------------------------------------------------------
+ * Continuous SAC (cleanrl/sac_continuous_action.py), ABI 43: a tanh-squashed Gaussian policy over
+ * float-vector actions, 1 <= A <= 64, on the TD3 block's replay and ocppo_polyak. All f32 unless
+ * stated, no atomics (the batch sums are f64 in a fixed order: bitwise repeatable),
+ * graph-capturable, one launch each. scale / bias / low / high are device arrays [A]; alpha is a
+ * device f32 scalar.
+ *
+ * Draws: Philox4x32-10 and the TD3 block's Box-Muller; counter words 0, 1 = row * 64 + a, word 2 =
+ *   the low 32 bits of the global step (acting) or of the replay's sample counter (updates), word 3
+ *   = the draw index (acting 0; updates: 0 the target's draw, 1 + 2 i the policy's draw of
+ *   iteration i, 2 + 2 i the temperature's), one key for acting and one for updates.
+ *   ocppo_csac_noise writes them: mode 0 the acting z, mode 1 the uniform phase's u in [0, 1), both
+ *   [rows, A] at t = counter[0] + offset; mode 2 the update stream's z of `draw` at sample counter
+ *   counter[0] + offset.
+ * ocppo_csac_act (:233-237) at global step t = step[0] + step_offset: t < learning_starts: uniform
+ *   in [low, high) per dimension; else mean = hidden W_mean^T + b_mean, r = hidden W_logstd^T +
+ *   b_logstd (hidden [E, H], H a multiple of 64, ocppo_td3_act's summation order), log_std = -5 +
+ *   3.5 (tanh(r) + 1), action = tanh(mean + exp(log_std) z) * scale + bias.
+ * ocppo_csac_sample_fwd (get_action, :138-150) from the heads' outputs mean, r [B, A] with the
+ *   update stream's z of `draw` at counter[0]: xa[:, D:] = tanh(x) * scale + bias, x = mean +
+ *   exp(log_std) z, into xa [B, D + A] (obs_act != NULL: its observation columns are copied into
+ *   xa, which is another buffer; NULL: left as they are); log_prob [B] = sum_a (-z^2 / 2 - log_std -
+ *   log sqrt(2 pi) - log(scale (1 - y^2) + 1e-6)), y = tanh(x), 1 - y^2 formed as 4 e / (1 + e)^2, e
+ *   = exp(-2 |x|) (accurate at any x, where 1 - y * y from the rounded y is not), summed in column
+ *   order; y_out,
+ *   z_out, log_std_out [B, A] for the backward, or all three NULL. xa NULL: log_prob alone. z_in
+ *   [B, A] != NULL: the draws are read from it (counter may then be NULL).
+ * ocppo_csac_sample_bwd: dxa [B, D + A] (its action columns are read), dlogp [B], the forward's
+ *   mean, r and outputs -> dmean, dr
+ *   [B, A]. The (x - mean)^2 / (2 sigma^2) term has zero gradient under the reparameterisation and
+ *   is not formed.
+ * ocppo_csac_critic_loss_fwd_bwd (:264-275): y = r + ((1 - d) * gamma) * (min(q1t, q2t) - alpha *
+ *   next_log_prob), dq = (2 / B)(q - y), stats [4] = {qf1_loss, qf2_loss, mean q1, mean q2}; y_out
+ *   [B] or NULL. With alpha = 0 and q2 = q1 bitwise ocppo_td3_critic_loss_fwd_bwd's twin form.
+ * ocppo_csac_actor_loss_fwd_bwd (:287-290): loss [1] = mean(alpha * log_prob - min(q1_pi, q2_pi)),
+ *   dlogp [B] = (1 / B) * alpha, dq1 / dq2 [B]: -(1 / B) to the smaller input and, where q1_pi ==
+ *   q2_pi, half of it to each (torch.min's backward).
+ * ocppo_csac_alpha_step (:296-304): loss [1] = mean(-exp(log_alpha) * (log_prob + target_entropy)),
+ *   torch.optim.Adam's step on log_alpha (exp_avg, exp_avg_sq [1] f32, adam_step [1] int64; the
+ *   step scalars formed in double) and alpha = exp(log_alpha).
+ * ------------------------------------------------------------------------------------------- */
+OCPPO_API int ocppo_csac_act(ocppo_stream_t stream, const float* hidden, int64_t E, int64_t H,
+                             const float* w_mean, const float* b_mean, const float* w_logstd,
+                             const float* b_logstd, int64_t A, const float* action_scale,
+                             const float* action_bias, const float* low, const float* high,
+                             uint64_t seed, const int64_t* step, int64_t step_offset,
+                             int64_t learning_starts, float* actions);
+OCPPO_API int ocppo_csac_noise(ocppo_stream_t stream, uint64_t seed, const int64_t* counter,
+                               int64_t offset, int64_t rows, int64_t A, int mode, int64_t draw,
+                               float* out);
+OCPPO_API int ocppo_csac_sample_fwd(ocppo_stream_t stream, const float* mean, const float* r,
+                                    int64_t B, int64_t D, int64_t A, const float* action_scale,
+                                    const float* action_bias, uint64_t seed,
+                                    const int64_t* counter, int64_t draw, const float* z_in,
+                                    const float* obs_act, float* xa, float* log_prob,
+                                    float* y_out, float* z_out, float* log_std_out);
+OCPPO_API int ocppo_csac_sample_bwd(ocppo_stream_t stream, const float* dxa, const float* dlogp,
+                                    const float* mean, const float* r, const float* y,
+                                    const float* z, const float* log_std, int64_t B, int64_t D,
+                                    int64_t A, const float* action_scale, float* dmean,
+                                    float* dr);
+OCPPO_API int ocppo_csac_critic_loss_fwd_bwd(ocppo_stream_t stream, const float* q1_next_target,
+                                             const float* q2_next_target, const float* q1,
+                                             const float* q2, const float* rewards,
+                                             const float* dones, const float* next_log_prob,
+                                             const float* alpha, int64_t B, double gamma,
+                                             float* dq1, float* dq2, float* stats, float* y_out);
+OCPPO_API int ocppo_csac_actor_loss_fwd_bwd(ocppo_stream_t stream, const float* q1_pi,
+                                            const float* q2_pi, const float* log_prob,
+                                            const float* alpha, int64_t B, float* dq1, float* dq2,
+                                            float* dlogp, float* loss);
+OCPPO_API int ocppo_csac_alpha_step(ocppo_stream_t stream, const float* log_prob, int64_t B,
+                                    float* alpha, float* log_alpha, double target_entropy,
+                                    float* exp_avg, float* exp_avg_sq, int64_t* adam_step,
+                                    double lr, double beta1, double beta2, double eps,
+                                    float* loss);
 
 #ifdef __cplusplus
 }

@@ -22,7 +22,7 @@ LIB_PATH = Path(os.environ.get("OCPPO_LIB", PKG / "lib" / "libocppo_hip.so"))
 HEADER = PKG.parent / "include" / "ocppo.h"
 
 # constants mirrored from include/ocppo.h (checked against the header by tests/test_abi.py)
-OCPPO_ABI_VERSION = 42
+OCPPO_ABI_VERSION = 43
 OCPPO_OK, OCPPO_E_INVALID, OCPPO_E_LAUNCH, OCPPO_E_WORKSPACE = 0, 1, 2, 3
 OCPPO_F32, OCPPO_BF16, OCPPO_U8 = 0, 1, 2
 OCPPO_X6_MBITS_ROWS = 2
@@ -204,6 +204,14 @@ SIGNATURES: dict[str, tuple[type, list]] = {
     "ocppo_td3_policy_actions_fwd": (I, [P, P, P, I64, I64, I64, P, P, P, P]),
     "ocppo_td3_policy_actions_bwd": (I, [P, P, P, I64, I64, I64, P, P]),
     "ocppo_polyak": (I, [P, I, P, P, P, D]),
+    "ocppo_csac_act": (I, [P, P, I64, I64, P, P, P, P, I64, P, P, P, P, U64, P, I64, I64, P]),
+    "ocppo_csac_noise": (I, [P, U64, P, I64, I64, I64, I, I64, P]),
+    "ocppo_csac_sample_fwd": (I, [P, P, P, I64, I64, I64, P, P, U64, P, I64, P, P, P, P, P, P,
+                                   P]),
+    "ocppo_csac_sample_bwd": (I, [P, P, P, P, P, P, P, P, I64, I64, I64, P, P, P]),
+    "ocppo_csac_critic_loss_fwd_bwd": (I, [P, P, P, P, P, P, P, P, P, I64, D, P, P, P, P]),
+    "ocppo_csac_actor_loss_fwd_bwd": (I, [P, P, P, P, P, I64, P, P, P, P]),
+    "ocppo_csac_alpha_step": (I, [P, P, I64, P, P, D, P, P, P, D, D, D, D, P]),
 }
 
 

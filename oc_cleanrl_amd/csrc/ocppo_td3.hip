@@ -9,7 +9,8 @@
 //   polyak                     t = tau * p + (1 - tau) * t over several flat buffers (:269-274)
 // f32 row arithmetic in torch's op order (the library is built with -ffp-contract=off), batch sums
 // in f64 in a fixed order (thread t takes rows t, t + 256, ..., then block_sum), no atomics, int64
-// row offsets, plain vector stores.
+// row offsets, plain vector stores. The stream conversions and the critic loss's rows are
+// ocppo_contq.h's, shared with ocppo_sac_cont.hip.
 //
 // Streams (all counter-based, so a captured graph draws fresh numbers on every replay):
 //   replay sample   h = splitmix64(splitmix64(seed ^ kContReplayKey) + counter * 0x100000001B3 +
@@ -19,30 +20,15 @@
 //   acting          Philox4x32-10, key seed ^ kTd3ActKey, counter (e * 64 + a, global step t):
 //                   word 0 -> the uniform phase's u in [0, 1), words 0 and 1 -> Box-Muller's z
 //   target noise    Philox4x32-10, key seed ^ kTd3TargetKey, counter (b * 64 + a, sample counter)
-#include "ocppo_common.h"
-#include "ocppo_philox.h"
+#include "ocppo_contq.h"
 #include "ocppo_rng.h"
 
 namespace ocppo {
 
-constexpr int kTd3MaxA = 64;  // ops.GAUSS_MAX_ACTIONS
-constexpr int kTd3Threads = 256;
 constexpr int kPolyakMaxPairs = 4;
 constexpr uint64_t kContReplayKey = 0x7D3C0A7B5E91F2A3ull;
 constexpr uint64_t kTd3ActKey = 0x7D3AC7E5B1F00D42ull;
 constexpr uint64_t kTd3TargetKey = 0x7D37A26E7C11A9B5ull;
-constexpr float kInv24 = 5.9604644775390625e-08f;  // 2^-24
-
-// top 24 bits of a Philox word as a uniform in [0, 1)
-__device__ __forceinline__ float unit24(uint32_t w) { return static_cast<float>(w >> 8) * kInv24; }
-
-// Box-Muller in f32: u1 in (0, 1] (so the logarithm is finite), u2 in [0, 1)
-__device__ __forceinline__ float box_muller(uint32_t w0, uint32_t w1) {
-  const float u1 = (static_cast<float>(w0 >> 8) + 1.0f) * kInv24;
-  const float u2 = unit24(w1);
-  const float r = sqrtf(-2.0f * logf(u1));
-  return r * cosf(6.2831855f * u2);
-}
 
 __device__ __forceinline__ uint4 act_words(uint64_t seed, int64_t t, int64_t e, int a) {
   return philox_block(seed ^ kTd3ActKey, static_cast<uint64_t>(t),
@@ -53,11 +39,6 @@ __device__ __forceinline__ float target_z(uint64_t seed, int64_t counter, int64_
   const uint4 r = philox_block(seed ^ kTd3TargetKey, static_cast<uint64_t>(counter),
                                static_cast<uint64_t>(b) * 64 + static_cast<uint64_t>(a));
   return box_muller(r.x, r.y);
-}
-
-// torch.clamp's value for a non-NaN input (a NaN stays a NaN)
-__device__ __forceinline__ float clamp_f(float v, float lo, float hi) {
-  return v != v ? v : fminf(fmaxf(v, lo), hi);
 }
 
 // ---- replay ------------------------------------------------------------------------------------------
@@ -229,34 +210,8 @@ __global__ __launch_bounds__(kTd3Threads) void td3_critic_kernel(
     const float* __restrict__ dones, int64_t B, float gamma, float norm, float* __restrict__ dq1,
     float* __restrict__ dq2, float* __restrict__ stats, float* __restrict__ y_out) {
   __shared__ double scratch[kTd3Threads / kWave];
-  const bool twin = q2 != nullptr;
-  double se1 = 0.0, se2 = 0.0, sq1 = 0.0, sq2 = 0.0;
-  for (int64_t b = threadIdx.x; b < B; b += kTd3Threads) {
-    const float m = twin ? fminf(q1t[b], q2t[b]) : q1t[b];
-    const float y = rewards[b] + ((1.0f - dones[b]) * gamma) * m;
-    if (y_out) y_out[b] = y;
-    const float o1 = q1[b], d1 = o1 - y;
-    se1 += static_cast<double>(d1 * d1);
-    sq1 += o1;
-    dq1[b] = norm * d1;
-    if (twin) {
-      const float o2 = q2[b], d2 = o2 - y;
-      se2 += static_cast<double>(d2 * d2);
-      sq2 += o2;
-      dq2[b] = norm * d2;
-    }
-  }
-  se1 = block_sum(se1, scratch);
-  se2 = block_sum(se2, scratch);
-  sq1 = block_sum(sq1, scratch);
-  sq2 = block_sum(sq2, scratch);
-  if (threadIdx.x == 0) {
-    const double fb = static_cast<double>(B);
-    stats[0] = static_cast<float>(se1 / fb);  // losses/qf1_loss
-    stats[1] = static_cast<float>(se2 / fb);  // losses/qf2_loss
-    stats[2] = static_cast<float>(sq1 / fb);  // losses/qf1_values
-    stats[3] = static_cast<float>(sq2 / fb);  // losses/qf2_values
-  }
+  critic_loss_rows<false>(q1t, q2t, q1, q2, rewards, dones, nullptr, 0.f, B, gamma, norm, dq1, dq2,
+                          stats, y_out, scratch);
 }
 
 // ---- the actor loss's action (:263) -------------------------------------------------------------------
@@ -329,13 +284,6 @@ __global__ __launch_bounds__(kTd3Threads) void polyak_kernel(PolyakArgs P, float
     const float b = keep * dst[i];
     dst[i] = a + b;
   }
-}
-
-static int td3_sizes(const char* who, int64_t B, int64_t D, int64_t A) {
-  OCPPO_REQUIRE(B >= 0 && D >= 1 && A >= 1 && A <= kTd3MaxA,
-                "%s: bad sizes B=%lld D=%lld A=%lld (D >= 1, 1 <= A <= %d)", who, (long long)B,
-                (long long)D, (long long)A, kTd3MaxA);
-  return OCPPO_OK;
 }
 
 }  // namespace ocppo

@@ -4279,3 +4279,218 @@ def polyak_(pairs, tau: float):
     c = ctypes
     call("ocppo_polyak", _stream(dev), n, (c.c_void_p * n)(*ps), (c.c_void_p * n)(*ts),
          (c.c_int64 * n)(*ns), float(tau))
+
+
+# ---------------------------------------------------------------------------------------------
+# Continuous SAC (sac_continuous_action.py): acting, get_action on the heads' outputs, the
+# entropy-regularised critic loss, the actor loss and the temperature step
+# (csrc/ocppo_sac_cont.hip); the replay and the soft update are TD3's
+# ---------------------------------------------------------------------------------------------
+def csac_policy_draw(i: int) -> int:
+    """The draw index of the policy's sample in iteration i of a policy step (:286)."""
+    return 1 + 2 * int(i)
+
+
+def csac_alpha_draw(i: int) -> int:
+    """The draw index of the temperature's fresh sample in iteration i (:298)."""
+    return 2 + 2 * int(i)
+
+
+CSAC_TARGET_DRAW = 0  # the target's sample (:265)
+
+
+def _csac_heads(mean, r, who: str):
+    if mean.dim() != 2 or r.shape != mean.shape or not 1 <= mean.shape[1] <= GAUSS_MAX_ACTIONS:
+        raise ValueError(f"{who}: mean {tuple(mean.shape)} against r {tuple(r.shape)} (A at most "
+                         f"{GAUSS_MAX_ACTIONS})")
+    return mean.shape
+
+
+def csac_act(hidden, w_mean, b_mean, w_logstd, b_logstd, action_scale, action_bias, low, high,
+             seed: int, step, learning_starts: int, actions_out=None, step_offset: int = 0):
+    """sac_continuous_action.py:233-237 at global step t = step[0] + step_offset, from the actor's
+    last hidden [E, H] (H a multiple of 64): t < learning_starts: uniform in [low, high) per
+    dimension; otherwise tanh(mean + exp(log_std) * z) * scale + bias with both heads in
+    td3.act_mu's summation order and log_std = -5 + 3.5 * (tanh(r) + 1). One launch; the branch is
+    taken on the device. csac_noise returns z (and the uniform u)."""
+    if hidden.dim() != 2 or w_mean.dim() != 2 or w_mean.shape[1] != hidden.shape[1] or \
+            w_logstd.shape != w_mean.shape:
+        raise ValueError(f"csac_act: hidden {tuple(hidden.shape)} against w_mean "
+                         f"{tuple(w_mean.shape)}, w_logstd {tuple(w_logstd.shape)}")
+    E, H = hidden.shape
+    A = w_mean.shape[0]
+    if not 1 <= A <= GAUSS_MAX_ACTIONS:
+        raise ValueError(f"csac_act: A = {A} action dimensions, at most {GAUSS_MAX_ACTIONS}")
+    if H % 64:
+        raise ValueError(f"csac_act: hidden width {H} is not a multiple of 64")
+    dev, f = hidden.device, torch.float32
+    if actions_out is None:
+        actions_out = torch.empty((E, A), dtype=f, device=dev)
+    call("ocppo_csac_act", _stream(dev), _check(hidden, "hidden", f), E, H,
+         _check(w_mean, "w_mean", f, dev, A * H), _check(b_mean, "b_mean", f, dev, A),
+         _check(w_logstd, "w_logstd", f, dev, A * H), _check(b_logstd, "b_logstd", f, dev, A), A,
+         _td3_vec(action_scale, "action_scale", A, dev), _td3_vec(action_bias, "action_bias", A, dev),
+         _td3_vec(low, "low", A, dev), _td3_vec(high, "high", A, dev),
+         int(seed) & 0xFFFFFFFFFFFFFFFF, _check(step, "step", torch.int64, dev, 1),
+         int(step_offset), int(learning_starts), _check(actions_out, "actions", f, dev, E * A))
+    return actions_out
+
+
+def csac_noise(seed: int, counter, rows: int, A: int, draw: int | None = None, offset: int = 0,
+               uniform: bool = False, out=None):
+    """The [rows, A] draws of the continuous-SAC streams. draw None: the acting stream at global
+    step counter[0] + offset (the standard normal z, or with `uniform` the random phase's u);
+    draw >= 0: the update stream's z of that draw index (CSAC_TARGET_DRAW, csac_policy_draw(i),
+    csac_alpha_draw(i)) at sample counter counter[0] + offset."""
+    dev = counter.device
+    if not 1 <= A <= GAUSS_MAX_ACTIONS:
+        raise ValueError(f"csac_noise: A = {A}, expected 1..{GAUSS_MAX_ACTIONS}")
+    if draw is not None and uniform:
+        raise ValueError("csac_noise: the uniform draw belongs to the acting stream (draw None)")
+    if out is None:
+        out = torch.empty((rows, A), dtype=torch.float32, device=dev)
+    mode = 2 if draw is not None else (1 if uniform else 0)
+    call("ocppo_csac_noise", _stream(dev), int(seed) & 0xFFFFFFFFFFFFFFFF,
+         _check(counter, "counter", torch.int64, dev, 1), int(offset), int(rows), A, mode,
+         int(draw or 0), _check(out, "out", torch.float32, dev, rows * A))
+    return out
+
+
+def _csac_sample_fwd(mean, r, action_scale, action_bias, seed, counter, draw, obs_act, xa, saved,
+                     z=None):
+    B, A = mean.shape
+    dev, f = mean.device, torch.float32
+    D = xa.shape[1] - A if xa is not None else 1
+    logp = torch.empty((B, 1), dtype=f, device=dev)
+    n = B * A
+    call("ocppo_csac_sample_fwd", _stream(dev), _check(mean, "mean", f, dev, n),
+         _check(r, "r", f, dev, n), B, D, A, _td3_vec(action_scale, "action_scale", A, dev),
+         _td3_vec(action_bias, "action_bias", A, dev), int(seed) & 0xFFFFFFFFFFFFFFFF,
+         _opt(counter, "counter", torch.int64, dev, 1), int(draw), _opt(z, "z", f, dev, n),
+         _opt(obs_act, "obs_act", f, dev, B * (D + A)), _opt(xa, "xa", f, dev, B * (D + A)),
+         logp.data_ptr(), *(t.data_ptr() if t is not None else None for t in saved))
+    return logp
+
+
+class _CsacSample(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mean, r, obs_act, action_scale, action_bias, seed, counter, draw, z_in):
+        B, A = mean.shape
+        xa = torch.empty_like(obs_act)
+        y, z, ls = (torch.empty_like(mean) for _ in range(3))
+        logp = _csac_sample_fwd(mean, r, action_scale, action_bias, seed, counter, draw, obs_act,
+                                xa, (y, z, ls), z_in)
+        ctx.save_for_backward(mean, r, y, z, ls, action_scale)
+        ctx.D = obs_act.shape[1] - A
+        ctx.mark_non_differentiable(y, z, ls)
+        return xa, logp, y, z, ls
+
+    @staticmethod
+    def backward(ctx, dxa, dlogp, *_):
+        mean, r, y, z, ls, scale = ctx.saved_tensors
+        B, A = y.shape
+        dev, f = y.device, torch.float32
+        dxa = torch.zeros((B, ctx.D + A), dtype=f, device=dev) if dxa is None else dxa.contiguous()
+        dlogp = torch.zeros((B, 1), dtype=f, device=dev) if dlogp is None else dlogp.contiguous()
+        dmean, dr = torch.empty_like(y), torch.empty_like(y)
+        call("ocppo_csac_sample_bwd", _stream(dev), _check(dxa, "dxa", f, dev, B * (ctx.D + A)),
+             _check(dlogp, "dlogp", f, dev, B), mean.data_ptr(), r.data_ptr(), y.data_ptr(), z.data_ptr(),
+             ls.data_ptr(), B, ctx.D, A, scale.data_ptr(), dmean.data_ptr(), dr.data_ptr())
+        return dmean, dr, None, None, None, None, None, None, None
+
+
+def csac_sample(mean, r, obs_act, action_scale, action_bias, seed: int = 0, counter=None,
+                draw: int = 0, aux: bool = False, z=None):
+    """get_action (sac_continuous_action.py:138-150) on the heads' outputs mean, r [B, A] with
+    the update stream's draw `draw` at sample counter counter[0]: (xa, log_prob [B, 1]), xa a
+    [B, D + A] copy of obs_act with its action columns replaced by tanh(mean + exp(log_std) * z) *
+    scale + bias. Differentiable in mean and r (two launches in all). aux: also (y, z, log_std).
+    z [B, A]: the draws are these, not the stream's (then no counter is needed)."""
+    _csac_heads(mean, r, "csac_sample")
+    if z is None and counter is None:
+        raise ValueError("csac_sample: the stream's draw needs the device counter")
+    if obs_act.dim() != 2 or obs_act.shape[0] != mean.shape[0] or \
+            obs_act.shape[1] <= mean.shape[1]:
+        raise ValueError(f"csac_sample: mean {tuple(mean.shape)} against obs_act "
+                         f"{tuple(obs_act.shape)}")
+    xa, logp, y, z, ls = _CsacSample.apply(mean, r.contiguous(), obs_act, action_scale,
+                                           action_bias, seed, counter, draw, z)
+    return (xa, logp, y, z, ls) if aux else (xa, logp)
+
+
+def csac_sample_forward(mean, r, action_scale, action_bias, seed: int = 0, counter=None,
+                        draw: int = 0, xa=None, z=None):
+    """The forward-only mode of csac_sample, one launch, no graph: log_prob [B, 1] of the draw;
+    xa [B, D + A], if given, receives the action in its action columns (the target's
+    next_obs_act: its observation columns stay). z: as csac_sample."""
+    B, A = _csac_heads(mean, r, "csac_sample_forward")
+    if z is None and counter is None:
+        raise ValueError("csac_sample_forward: the stream's draw needs the device counter")
+    if xa is not None and (xa.dim() != 2 or xa.shape[0] != B or xa.shape[1] <= A):
+        raise ValueError(f"csac_sample_forward: mean {tuple(mean.shape)} against xa "
+                         f"{tuple(xa.shape)}")
+    return _csac_sample_fwd(mean, r, action_scale, action_bias, seed, counter, draw, None, xa,
+                            (None, None, None), z)
+
+
+def csac_critic_loss_fwd_bwd(q1t, q2t, q1, q2, rewards, dones, next_log_prob, alpha, gamma: float,
+                             dq1=None, dq2=None, stats=None, y_out=None):
+    """sac_continuous_action.py:264-275 from the four critic outputs and the next log-prob [B] (or
+    [B, 1]) and the device scalar alpha: (stats [4] = {qf1_loss, qf2_loss, mean q1, mean q2}, dq1,
+    dq2 = d qf_loss / d q); y = r + (1 - d) * gamma * (min(q1t, q2t) - alpha * next_log_prob)."""
+    B = q1.numel()
+    dev, f = q1.device, torch.float32
+    if dq1 is None:
+        dq1 = torch.empty_like(q1)
+    if dq2 is None:
+        dq2 = torch.empty_like(q2)
+    if stats is None:
+        stats = torch.empty(4, dtype=f, device=dev)
+    call("ocppo_csac_critic_loss_fwd_bwd", _stream(dev), _check(q1t, "q1t", f, dev, B),
+         _check(q2t, "q2t", f, dev, B), _check(q1, "q1", f, dev, B), _check(q2, "q2", f, dev, B),
+         _check(rewards, "rewards", f, dev, B), _check(dones, "dones", f, dev, B),
+         _check(next_log_prob, "next_log_prob", f, dev, B), _check(alpha, "alpha", f, dev, 1), B,
+         float(gamma), _check(dq1, "dq1", f, dev, B), _check(dq2, "dq2", f, dev, B),
+         _check(stats, "stats", f, dev, 4), _opt(y_out, "y_out", f, dev, B))
+    return stats, dq1, dq2
+
+
+def csac_actor_loss_fwd_bwd(q1_pi, q2_pi, log_prob, alpha, dq1=None, dq2=None, dlogp=None,
+                            loss=None):
+    """sac_continuous_action.py:287-290: (loss [1] = mean(alpha * log_prob - min(q1_pi, q2_pi)),
+    dq1, dq2, dlogp), the min's gradient routed as torch.min's backward (ties: half each)."""
+    B = q1_pi.numel()
+    dev, f = q1_pi.device, torch.float32
+    if dq1 is None:
+        dq1 = torch.empty_like(q1_pi)
+    if dq2 is None:
+        dq2 = torch.empty_like(q2_pi)
+    if dlogp is None:
+        dlogp = torch.empty_like(log_prob)
+    if loss is None:
+        loss = torch.empty(1, dtype=f, device=dev)
+    call("ocppo_csac_actor_loss_fwd_bwd", _stream(dev), _check(q1_pi, "q1_pi", f, dev, B),
+         _check(q2_pi, "q2_pi", f, dev, B), _check(log_prob, "log_prob", f, dev, B),
+         _check(alpha, "alpha", f, dev, 1), B, _check(dq1, "dq1", f, dev, B),
+         _check(dq2, "dq2", f, dev, B), _check(dlogp, "dlogp", f, dev, B),
+         _check(loss, "loss", f, dev, 1))
+    return loss, dq1, dq2, dlogp
+
+
+def csac_alpha_step(log_prob, temp: SacTemperature, loss=None):
+    """sac_continuous_action.py:296-304 on the fresh draw's log_prob [B]: loss [1] =
+    mean(-exp(log_alpha) * (log_prob + target_entropy)), log_alpha's Adam step and alpha =
+    exp(log_alpha) on temp's buffers, one launch. temp.autotune only."""
+    if not temp.autotune:
+        raise ValueError("csac_alpha_step: the temperature is a constant (autotune off)")
+    B = log_prob.numel()
+    dev, f = log_prob.device, torch.float32
+    if loss is None:
+        loss = torch.empty(1, dtype=f, device=dev)
+    call("ocppo_csac_alpha_step", _stream(dev), _check(log_prob, "log_prob", f, dev, B), B,
+         _check(temp.alpha, "alpha", f, dev, 1), _check(temp.log_alpha, "log_alpha", f, dev, 1),
+         temp.target_entropy, _check(temp.exp_avg, "exp_avg", f, dev, 1),
+         _check(temp.exp_avg_sq, "exp_avg_sq", f, dev, 1),
+         _check(temp.step, "adam_step", torch.int64, dev, 1), temp.lr, temp.betas[0],
+         temp.betas[1], temp.eps, _check(loss, "loss", f, dev, 1))
+    return loss

@@ -226,24 +226,10 @@ class TD3Trainer:
 
     def __init__(self, args, device, log: bool = True, device_env=None):
         a = args
-        if a.backend != "Synthetic":
-            raise NotImplementedError("MuJoCo / gymnasium are not available; use --backend "
-                                      "Synthetic")
-        if device_env is None and a.env_id != "Pendulum-v1":
-            raise NotImplementedError(f"env_id {a.env_id!r}: the device env with a continuous "
-                                      "action is Pendulum-v1 (MuJoCo is not available)")
-        if device_env is not None and device_env.n_actions > ops.GAUSS_MAX_ACTIONS:
-            raise ValueError(f"{device_env.n_actions} action dimensions: the TD3 kernels take at "
-                             f"most {ops.GAUSS_MAX_ACTIONS}")
-        if a.policy_frequency < 1:
-            raise ValueError(f"policy_frequency = {a.policy_frequency} must be at least 1")
-        if a.batch_size < 1:
-            raise ValueError(f"batch_size = {a.batch_size} must be at least 1")
+        self._refuse(a, device_env)
         self.args = a
-        self.twin = bool(a.twin)
-        self.fused = FUSED_TD3
+        self._configure(a)
         self.learning_starts = int(a.learning_starts)
-        self.policy_noise = float(a.policy_noise) if self.twin else 0.0
         self.dev = dev = torch.device(device)
         torch.use_deterministic_algorithms(a.torch_deterministic)
         torch.utils.deterministic.fill_uninitialized_memory = False  # see dqn.DQNTrainer
@@ -258,13 +244,7 @@ class TD3Trainer:
         self.A = A = int(env.n_actions)
         self.D = D = int(env.frame.shape[1])
         spec = box_spec(D, env.action_low, env.action_high)
-        actor, q, target_actor, q_target = make_networks(spec, self.twin)
-        self.actor, self.q = actor.to(dev), q.to(dev)
-        self.target_actor, self.target = target_actor.to(dev), q_target.to(dev)
-        self.q_opt = ops.FlatAdam(self.q.parameters(), lr=a.learning_rate)          # :187
-        self.actor_opt = ops.FlatAdam(self.actor.parameters(), lr=a.learning_rate)  # :188
-        self.tq_flat = _flat_target(self.target, dev)
-        self.ta_flat = _flat_target(self.target_actor, dev)
+        self._build_networks(spec)
         self.actor_params = list(self.actor.parameters())
         f32 = torch.float32
         sp = spec.single_action_space
@@ -281,13 +261,57 @@ class TD3Trainer:
         self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)  # the chunk's first step
         self.dq1 = torch.zeros((B, 1), dtype=f32, device=dev)
         self.dq2 = torch.zeros((B, 1), dtype=f32, device=dev) if self.twin else None
-        self.dqa = torch.full((B, 1), -(1.0 / B), dtype=f32, device=dev)  # d (-q.mean()) / d q
         self.q_stats = torch.zeros(4, dtype=f32, device=dev)
-        self.pi_q = torch.zeros((B, 1), dtype=f32, device=dev)  # qf1(s, actor(s)) of :263
+        self._build_policy_buffers(B)
         self.global_step = 0  # the next step's index = the steps taken
         self.log_enabled = log
         self.graphs: dict = {}
         self.obs.copy_(env.reset())  # :202
+
+    # ---- what a learner on this loop (sac_continuous.ContSACTrainer) replaces -------------------
+    WHO = "TD3"
+    CHUNK_NAME = "policy_frequency"  # what chunk_len is, in steps()'s refusal
+
+    def _refuse(self, a, device_env):
+        """Every refusal, before any device work."""
+        if a.backend != "Synthetic":
+            raise NotImplementedError("MuJoCo / gymnasium are not available; use --backend "
+                                      "Synthetic")
+        if device_env is None and a.env_id != "Pendulum-v1":
+            raise NotImplementedError(f"env_id {a.env_id!r}: the device env with a continuous "
+                                      "action is Pendulum-v1 (MuJoCo is not available)")
+        if device_env is not None and device_env.n_actions > ops.GAUSS_MAX_ACTIONS:
+            raise ValueError(f"{device_env.n_actions} action dimensions: the {self.WHO} kernels "
+                             f"take at most {ops.GAUSS_MAX_ACTIONS}")
+        if a.policy_frequency < 1:
+            raise ValueError(f"policy_frequency = {a.policy_frequency} must be at least 1")
+        if a.batch_size < 1:
+            raise ValueError(f"batch_size = {a.batch_size} must be at least 1")
+
+    def _configure(self, a):
+        self.twin = bool(a.twin)
+        self.fused = FUSED_TD3
+        self.policy_noise = float(a.policy_noise) if self.twin else 0.0
+
+    def _build_networks(self, spec):
+        a, dev = self.args, self.dev
+        actor, q, target_actor, q_target = make_networks(spec, self.twin)
+        self.actor, self.q = actor.to(dev), q.to(dev)
+        self.target_actor, self.target = target_actor.to(dev), q_target.to(dev)
+        self.q_opt = ops.FlatAdam(self.q.parameters(), lr=a.learning_rate)          # :187
+        self.actor_opt = ops.FlatAdam(self.actor.parameters(), lr=a.learning_rate)  # :188
+        self.tq_flat = _flat_target(self.target, dev)
+        self.ta_flat = _flat_target(self.target_actor, dev)
+
+    def _build_policy_buffers(self, B: int):
+        f32, dev = torch.float32, self.dev
+        self.dqa = torch.full((B, 1), -(1.0 / B), dtype=f32, device=dev)  # d (-q.mean()) / d q
+        self.pi_q = torch.zeros((B, 1), dtype=f32, device=dev)  # qf1(s, actor(s)) of :263
+
+    @property
+    def chunk_len(self) -> int:
+        """The global steps of one graph chunk: the period of the train step's schedule."""
+        return self.args.policy_frequency
 
     # ---- acting --------------------------------------------------------------------------------
     def _act(self, k: int):
@@ -407,18 +431,18 @@ class TD3Trainer:
             self._train_step(policy)
 
     def _chunk(self, base: int):
-        pf = self.args.policy_frequency
-        for k in range(pf):
+        n = self.chunk_len
+        for k in range(n):
             self._step(k, base + k)
-        self.env.advance(pf)
-        self.step_dev.add_(pf)
+        self.env.advance(n)
+        self.step_dev.add_(n)
 
     def _graphable(self) -> bool:
         return bool(self.args.cuda_graphs)
 
     def _run_chunk(self, base: int):
-        pf, ls = self.args.policy_frequency, self.learning_starts
-        if base + pf - 1 <= ls:
+        n, ls = self.chunk_len, self.learning_starts
+        if base + n - 1 <= ls:
             key = "fill"   # no step of the chunk trains
         elif base > ls:
             key = "train"  # every step trains; the policy step is the chunk's first
@@ -439,14 +463,14 @@ class TD3Trainer:
     def steps(self, n: int):
         """Advance `n` global steps; with graphs, n and the steps already taken are multiples of
         policy_frequency (a chunk is policy_frequency steps starting at such a multiple)."""
-        pf = self.args.policy_frequency
+        c = self.chunk_len
         if self._graphable():
-            if n % pf or self.global_step % pf:
+            if n % c or self.global_step % c:
                 raise ValueError(f"n={n} (after {self.global_step} steps) must be a multiple of "
-                                 f"policy_frequency={pf}")
-            for _ in range(n // pf):
+                                 f"{self.CHUNK_NAME}={c}")
+            for _ in range(n // c):
                 self._run_chunk(self.global_step)
-                self.global_step += pf
+                self.global_step += c
             return
         for _ in range(n):  # the script's order step by step
             self._step(0, self.global_step)
