@@ -16,7 +16,8 @@ import math
 import torch
 
 from . import _lib
-from ._lib import OCPPO_BF16, OCPPO_F32, OCPPO_U8, STAT_NAMES, call
+from ._lib import (OCPPO_BF16, OCPPO_F32, OCPPO_NET_CHANNELS_LAST, OCPPO_NET_SCALE_255, OCPPO_U8,
+                   STAT_NAMES, call)
 
 _DTYPE_CODE = {torch.float32: OCPPO_F32, torch.bfloat16: OCPPO_BF16, torch.uint8: OCPPO_U8}
 
@@ -44,8 +45,8 @@ def _opt(t, *a, **k) -> int | None:
 
 def _net_obs(net_obs, N: int, W: int, D: int, device):
     """(pointer, layout) of a rollout network-input buffer: a contiguous [N, W, ...] f32 tensor
-    (layout 0) or a channels_last [N, W, H, X] one (layout 1: memory [N, H, X, W], the NHWC input
-    of a channels_last NatureCNN)."""
+    (layout 0) or a channels_last [N, W, H, X] one (layout OCPPO_NET_CHANNELS_LAST: memory
+    [N, H, X, W], the NHWC input of a channels_last NatureCNN)."""
     if net_obs is None:
         return None, 0
     if net_obs.is_contiguous():
@@ -54,7 +55,7 @@ def _net_obs(net_obs, N: int, W: int, D: int, device):
             tuple(net_obs.shape[:2]) == (N, W) and net_obs[0, 0].numel() == D:
         if net_obs.dtype != torch.float32 or net_obs.device != device:
             raise ValueError(f"net_obs: expected float32 on {device}")
-        return net_obs.data_ptr(), 1
+        return net_obs.data_ptr(), OCPPO_NET_CHANNELS_LAST
     raise ValueError("net_obs must be contiguous [N, W, ...] or channels_last [N, W, H, X]")
 
 
@@ -354,7 +355,7 @@ class _PPOLoss(torch.autograd.Function):
         ctx.save_for_backward(dlogits, dvalue)
         ctx.value_shape = new_value.shape
         ctx.mark_non_differentiable(stats)
-        loss = stats[0].clone()
+        loss = stats[_lib.OCPPO_STAT_LOSS].clone()
         return loss, stats
 
     @staticmethod
@@ -607,7 +608,8 @@ def rollout_store(frame, reward, done, prev_obs, obs_out, net_obs=None, reward_o
          _check(done, "done", f, dev, N), N, W, D, _check(prev_obs, "prev_obs", None, dev),
          _check(obs_out, "obs_out", None, dev), _DTYPE_CODE[obs_out.dtype], net,
          _opt(reward_out, "reward_out", f, dev, N), _opt(done_out, "done_out", f, dev, N),
-         layout | (2 if scale255 else 0), _reset_prev(reset_prev, frame, N, W, D, dev))
+         layout | (OCPPO_NET_SCALE_255 if scale255 else 0),
+         _reset_prev(reset_prev, frame, N, W, D, dev))
 
 
 def rollout_store_vecnorm(frame, reward, done, prev_obs, obs_out, net_obs, done_out, ret_state,
@@ -631,7 +633,8 @@ def rollout_store_vecnorm(frame, reward, done, prev_obs, obs_out, net_obs, done_
          float(gamma), float(epsilon), float(clip_reward),
          _check(ret_state, "ret_state", torch.float64, dev, N),
          _check(rms_state, "rms_state", torch.float64, dev, 3),
-         _check(reward_out, "reward_out", f, dev, N), layout | (2 if scale255 else 0),
+         _check(reward_out, "reward_out", f, dev, N),
+         layout | (OCPPO_NET_SCALE_255 if scale255 else 0),
          _reset_prev(reset_prev, frame, N, W, D, dev))
 
 
@@ -644,7 +647,7 @@ def obs_reset(frame, obs_out, net_obs=None, scale255: bool = False):
     net, layout = _net_obs(net_obs, N, W, D, dev)
     call("ocppo_obs_reset", _stream(dev), _check(frame, "frame", None, dev),
          _DTYPE_CODE[frame.dtype], N, W, D, _check(obs_out, "obs_out", None, dev),
-         _DTYPE_CODE[obs_out.dtype], net, layout | (2 if scale255 else 0))
+         _DTYPE_CODE[obs_out.dtype], net, layout | (OCPPO_NET_SCALE_255 if scale255 else 0))
 
 
 def linear_act(x, weight, bias=None, relu: bool = False, out=None, ring=None):
@@ -787,7 +790,11 @@ def _geom(*v):
 # loaded with OCPPO_LIB=OUT.so; never the product): before every convolution launch the library
 # is handed the extents of the sources its gathers read, from the pointers it is passed, and a
 # device record of the first out-of-range index (tests/test_conv_bounds_gpu.py reads it).
-X6_BOUNDS = hasattr(_lib.LIB, "ocppo_x6_probe_set_bounds")
+# The probe is no part of the C-ABI (the header does not declare it), hence the lookup by name.
+_X6_PROBE = getattr(_lib.LIB, "ocppo_x6_probe_set_bounds", None)
+X6_BOUNDS = _X6_PROBE is not None
+if X6_BOUNDS:
+    _X6_PROBE.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]
 BOUND_KINDS = {1: "f32 source offset", 2: "image index", 3: "u8 stack row", 4: "u8 byte offset"}
 
 
@@ -811,11 +818,8 @@ def __getattr__(name):
 
 def _bounds(dev, x=None, u8=None):
     if X6_BOUNDS:
-        _lib.LIB.ocppo_x6_probe_set_bounds.argtypes = [ctypes.c_void_p, ctypes.c_int64,
-                                                       ctypes.c_int64, ctypes.c_int64]
-        _lib.LIB.ocppo_x6_probe_set_bounds(
-            bounds_record(dev).data_ptr(), _tail(x) if x is not None else 0,
-            _tail(u8) if u8 is not None else 0, u8.shape[0] if u8 is not None else 0)
+        _X6_PROBE(bounds_record(dev).data_ptr(), _tail(x) if x is not None else 0,
+                  _tail(u8) if u8 is not None else 0, u8.shape[0] if u8 is not None else 0)
 
 
 def _conv_rows_form(M: int, Cout: int) -> bool:
@@ -2157,7 +2161,7 @@ def gather_rows(src, idx, out=None, scale255: bool = False):
         C = src.shape[1]
         call("ocppo_gather_rows_cl", _stream(dev), _check(src, "src", None, dev),
              _DTYPE_CODE[src.dtype], _check(idx, "idx", torch.int64, dev, M), M, C, R // C,
-             out.data_ptr(), 2 if scale255 else 0)
+             out.data_ptr(), OCPPO_NET_SCALE_255 if scale255 else 0)
         return out
     if scale255:
         raise ValueError("scale255 needs a channels_last out (ocppo_gather_rows_cl)")
@@ -2222,7 +2226,8 @@ def cartpole_step(seed: int, actions, state, counters, obs_out, reward_out=None,
 # ---------------------------------------------------------------------------------------------
 # clip_grad_norm_ + Adam over flat buffers (ppo_atari_oc.py:608-610)
 # ---------------------------------------------------------------------------------------------
-OPT_STEP, OPT_TOTAL_NORM, OPT_CLIP_COEF = 0, 1, 2
+OPT_STEP, OPT_TOTAL_NORM, OPT_CLIP_COEF = (_lib.OCPPO_OPT_STEP, _lib.OCPPO_OPT_TOTAL_NORM,
+                                           _lib.OCPPO_OPT_CLIP_COEF)
 
 
 FLAT_ALIGN = 64  # floats: every parameter / grad view in a flat buffer starts 256-B aligned
@@ -2275,7 +2280,7 @@ class FlatAdam:
         self.exp_avg = torch.zeros_like(self.params)
         self.exp_avg_sq = torch.zeros_like(self.params)
         self.lr = torch.tensor(float(lr), dtype=torch.float32, device=dev)
-        self.scalars = torch.zeros(8, dtype=torch.float32, device=dev)
+        self.scalars = torch.zeros(_lib.OCPPO_OPT_NUM_SCALARS, dtype=torch.float32, device=dev)
         self.betas = (float(betas[0]), float(betas[1]))
         self.eps = float(eps)
         self.max_grad_norm = float(max_grad_norm)
@@ -3773,7 +3778,7 @@ def ppg_aux_gather(aux_obs, aux_pi, aux_returns, cols, out_obs=None, out_pi=None
     return out_obs, out_pi, out_returns
 
 
-OPT_TAIL_SKIPPED, OPT_TAIL_STEP = 6, 7
+OPT_TAIL_SKIPPED, OPT_TAIL_STEP = _lib.OCPPO_OPT_TAIL_SKIPPED, _lib.OCPPO_OPT_TAIL_STEP
 
 
 class FlatAdamSegments(FlatAdam):

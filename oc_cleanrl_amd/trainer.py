@@ -32,7 +32,7 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
-from . import agents, frames, gemm_table, ops, rccl
+from . import _lib, agents, frames, gemm_table, ops, rccl
 from .rccl import RcclComm, RcclExchange
 from .agents import NormalizeImg, PPObj, fused_trunk, linear_relu, make_agent
 from .args import Args, env_rank, parse_dataclass
@@ -1142,7 +1142,7 @@ class PPOTrainer:
                 self._update_epoch(e)
             self.executed_mb += self.nmb
             if a.target_kl is not None:
-                kl = float(self.stats[e * self.nmb + self.nmb - 1, 5])
+                kl = float(self.stats[e * self.nmb + self.nmb - 1, _lib.OCPPO_STAT_APPROX_KL])
                 if kl > a.target_kl:
                     if e + 1 < self.E:
                         self._rewind_shuffle(e + 1)
@@ -1234,14 +1234,15 @@ class PPOTrainer:
         last = stats[-1]
         m = {
             "charts/learning_rate": lr,
-            "losses/value_loss": float(last[2]),
-            "losses/policy_loss": float(last[1]),
-            "losses/entropy": float(last[3]),
-            "losses/old_approx_kl": float(last[4]),
-            "losses/approx_kl": float(last[5]),
-            "losses/clipfrac": float(np.mean(stats[:, 6].astype(np.float32))),
+            "losses/value_loss": float(last[_lib.OCPPO_STAT_V_LOSS]),
+            "losses/policy_loss": float(last[_lib.OCPPO_STAT_PG_LOSS]),
+            "losses/entropy": float(last[_lib.OCPPO_STAT_ENTROPY]),
+            "losses/old_approx_kl": float(last[_lib.OCPPO_STAT_OLD_APPROX_KL]),
+            "losses/approx_kl": float(last[_lib.OCPPO_STAT_APPROX_KL]),
+            "losses/clipfrac": float(np.mean(
+                stats[:, _lib.OCPPO_STAT_CLIPFRAC].astype(np.float32))),
             "losses/explained_variance": float("nan") if var_y == 0 else ev,
-            "losses/loss": float(last[0]),
+            "losses/loss": float(last[_lib.OCPPO_STAT_LOSS]),
         }
         if ep_n > 0:
             m["charts/Episodic_Original_Reward"] = ep_ret / ep_n
@@ -1263,14 +1264,14 @@ class PPOTrainer:
         last = stats[-1]
         m = {
             "charts/learning_rate": float(self.lr),
-            "losses/value_loss": float(last[2]),
-            "losses/policy_loss": float(last[1]),
-            "losses/entropy": float(last[3]),
-            "losses/old_approx_kl": float(last[4]),
-            "losses/approx_kl": float(last[5]),
-            "losses/clipfrac": float(np.mean(stats[:, 6])),
+            "losses/value_loss": float(last[_lib.OCPPO_STAT_V_LOSS]),
+            "losses/policy_loss": float(last[_lib.OCPPO_STAT_PG_LOSS]),
+            "losses/entropy": float(last[_lib.OCPPO_STAT_ENTROPY]),
+            "losses/old_approx_kl": float(last[_lib.OCPPO_STAT_OLD_APPROX_KL]),
+            "losses/approx_kl": float(last[_lib.OCPPO_STAT_APPROX_KL]),
+            "losses/clipfrac": float(np.mean(stats[:, _lib.OCPPO_STAT_CLIPFRAC])),
             "losses/explained_variance": float("nan") if float(var_y) == 0 else float(ev),
-            "losses/loss": float(last[0]),
+            "losses/loss": float(last[_lib.OCPPO_STAT_LOSS]),
         }
         if ep_n > 0:
             m["charts/Episodic_Original_Reward"] = ep_ret / ep_n

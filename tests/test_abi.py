@@ -36,6 +36,127 @@ def test_header_constants_match_python(lib):
     assert [n.lower() for n, _ in sorted(stat_names, key=lambda x: int(x[1]))] == list(lib.STAT_NAMES)
 
 
+SYNTHETIC_HEADER = """
+/* a comment with a call in it: ocppo_ghost(int x); and an unbalanced ( too */
+#ifndef OCPPO_H
+#define OCPPO_H
+#define OCPPO_ABI_VERSION 7
+#define OCPPO_STAT_B 1 /* second (by value) */
+#define OCPPO_STAT_A 0 // first: ocppo_other(
+#define OCPPO_NOT_DECIMAL 0x10
+#define OCPPO_API __attribute__((visibility("default")))
+typedef void* ocppo_stream_t; /* hipStream_t */
+OCPPO_API int ocppo_version(void);
+OCPPO_API const char* ocppo_message(void);
+// OCPPO_API int ocppo_commented_out(int x);
+OCPPO_API int ocppo_many(ocppo_stream_t stream, const float* const* src,  /* ( */
+                         void* const* dst, float scale,
+                         uint32_t seed, int64_t n,
+                         uint64_t key, double lr, size_t bytes, int flag);
+OCPPO_API size_t ocppo_bytes(int64_t n);
+OCPPO_API int64_t
+ocppo_chunks(int64_t n);
+#endif
+"""
+
+
+def test_parse_header_on_synthetic_text(lib):
+    c = ctypes
+    sigs, consts = lib.parse_header(SYNTHETIC_HEADER)
+    assert sigs == {
+        "ocppo_version": (c.c_int, []),
+        "ocppo_message": (c.c_char_p, []),
+        "ocppo_many": (c.c_int, [c.c_void_p, c.c_void_p, c.c_void_p, c.c_float, c.c_uint32,
+                                 c.c_int64, c.c_uint64, c.c_double, c.c_size_t, c.c_int]),
+        "ocppo_bytes": (c.c_size_t, [c.c_int64]),
+        "ocppo_chunks": (c.c_int64, [c.c_int64]),
+    }
+    assert consts == {"OCPPO_ABI_VERSION": 7, "OCPPO_STAT_B": 1, "OCPPO_STAT_A": 0}
+
+
+@pytest.mark.parametrize("decl, names", [
+    ("OCPPO_API int ocppo_f(const float* x, long count);", ("ocppo_f", "count")),  # unknown scalar
+    ("OCPPO_API int ocppo_f(unsigned int count);", ("ocppo_f", "count")),
+    ("OCPPO_API int ocppo_f(ocppo_deferred_finish_t rec);", ("ocppo_f", "rec")),  # struct by value
+    ("OCPPO_API int ocppo_f(int64_t n, float taps[4]);", ("ocppo_f", "taps")),  # array
+    ("OCPPO_API int ocppo_f(float taps[]);", ("ocppo_f", "taps")),
+    ("OCPPO_API int ocppo_f(void (*done)(int));", ("ocppo_f", "done")),  # function pointer
+    ("OCPPO_API int ocppo_f(int64_t);", ("ocppo_f", "int64_t")),  # unnamed parameter
+    ("OCPPO_API void ocppo_f(int64_t n);", ("ocppo_f", "return")),  # no status to check
+    ("OCPPO_API long ocppo_f(int64_t n);", ("ocppo_f", "return")),
+])
+def test_parse_header_refuses_what_it_cannot_map(lib, decl, names):
+    with pytest.raises(ImportError) as e:
+        lib.parse_header(decl)
+    for n in names:
+        assert n in str(e.value)
+
+
+def test_parse_header_refuses_a_declaration_it_cannot_read(lib):
+    with pytest.raises(ImportError):
+        lib.parse_header("OCPPO_API int (*ocppo_f(int64_t n))(int);")
+    with pytest.raises(ImportError):  # a name declared twice
+        lib.parse_header("OCPPO_API int ocppo_f(int64_t n);\nOCPPO_API int ocppo_f(int n);")
+
+
+def test_pinned_signatures(lib):
+    """Literal copies of the hand-typed table this binding once held, for entries that between
+    them use every mapped type: the parser must keep deriving exactly these."""
+    P, I64, U64, D, I, SZ = (ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_double,
+                             ctypes.c_int, ctypes.c_size_t)
+    U32, F = ctypes.c_uint32, ctypes.c_float
+    pinned = {
+        "ocppo_last_error": (ctypes.c_char_p, []),
+        "ocppo_ppo_loss_workspace_bytes": (SZ, [I64, I64]),
+        "ocppo_gae": (I, [P, P, P, P, P, P, I64, I64, D, D, P, P]),
+        "ocppo_dropout": (I, [P, P, P, I64, U32, F, I64, P]),
+        "ocppo_conv_x6_u8": (I, [P, I, P, P, I64, I64, I64, I64, I64, I64, P, I64, P, I64, I64,
+                                 I64, I64, P, I, F, I, P, P, P, P]),
+        "ocppo_polyak": (I, [P, I, P, P, P, D]),
+        "ocppo_deferred_finish_run": (I, [P, P]),
+        "ocppo_relu_bias_grad_chunks": (I64, [I64, I64]),
+        "ocppo_replay_sample": (I, [P, U64, P, P, I64, I64, I64, P, I, P, P, P, I64, P, P, P, P,
+                                    P, P]),
+    }
+    for name, (restype, argtypes) in pinned.items():
+        assert lib.SIGNATURES[name] == (restype, argtypes), name
+        fn = getattr(lib.LIB, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+    used = {t for r, a in pinned.values() for t in [r, *a]}
+    assert used == {t for r, a in lib.SIGNATURES.values() for t in [r, *a]}
+
+
+def test_header_defines_are_module_constants(lib):
+    text = (ROOT / "include" / "ocppo.h").read_text()
+    consts = dict(re.findall(r"#define (OCPPO_\w+) (\d+)", text))
+    assert len(consts) >= 30
+    for name, value in consts.items():
+        assert getattr(lib, name) == int(value), name
+    from oc_cleanrl_amd import ops
+
+    assert (ops.OPT_STEP, ops.OPT_TOTAL_NORM, ops.OPT_CLIP_COEF, ops.OPT_TAIL_SKIPPED,
+            ops.OPT_TAIL_STEP) == (0, 1, 2, 6, 7)  # the header's values at ABI 43
+
+
+def test_call_sites_name_declared_entry_points(lib):
+    """Every entry point the package names -- a string literal (passed to call( directly, chosen
+    by a conditional, or kept as a class's ENTRY) or an attribute of LIB -- is declared in the
+    header: a typo in a rarely-taken path fails here, not on a GPU. Only a by-name
+    getattr(LIB, "...") is left out: that is how a probe build's symbol outside the C-ABI is
+    reached."""
+    named = {}
+    for src in sorted((ROOT / "oc_cleanrl_amd").glob("*.py")):
+        text = src.read_text()
+        pattern = r"\bLIB\.(ocppo_\w+)"
+        if src.name != "_lib.py":  # (whose string literals are the parser's type names)
+            pattern += r"|(?<!LIB, )[\"'](ocppo_\w+)[\"']"
+        for m in re.finditer(pattern, text):
+            named.setdefault(m.group(m.lastindex), src.name)
+    assert len(named) >= 100 and "ocppo_clip_radam_step" in named
+    unknown = {n: f for n, f in named.items() if n not in lib.SIGNATURES}
+    assert not unknown, unknown
+
+
 def test_only_c_abi_is_exported():
     import subprocess
 
