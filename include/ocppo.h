@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCPPO_ABI_VERSION 43
+#define OCPPO_ABI_VERSION 44
 
 /* status codes */
 #define OCPPO_OK 0
@@ -1865,6 +1865,37 @@ OCPPO_API int ocppo_csac_alpha_step(ocppo_stream_t stream, const float* log_prob
                                     float* exp_avg, float* exp_avg_sq, int64_t* adam_step,
                                     double lr, double beta1, double beta2, double eps,
                                     float* loss);
+
+/* ---------------------------------------------------------------------------------------------
+ * MaDi's masker (architectures/madi.py MaskerNet with three layers; cleanrl/ppo_atari_madi.py:441,
+ * :502), fused per image tile (ABI 44): y = x * sigmoid(conv3(relu(conv2(relu(conv1(x / 255)))))),
+ * every frame of a stack on its own, 3x3 zero-padded convolutions 1 -> F -> F -> 1, F 16 or 32.
+ *   src      : the frame stacks [rows, W, H, H], u8 or f32 (src_dtype OCPPO_U8 / OCPPO_F32)
+ *   idx      : [B] int64 rows of src (an index outside [0, rows) is clamped into it, never
+ *              dereferenced), or NULL: rows 0 .. B - 1
+ *   w1 [F,1,3,3] b1 [F] w2 [F,F,3,3] b2 [F] w3 [1,F,3,3] b3 [1] : f32, contiguous
+ *   out / g  : the masked stacks [B, W, H, H] f32 / their gradient, memory [B][W][H][H]
+ *              (channels_last 0) or [B][H][H][W] (channels_last 1)
+ * ocppo_madi_mask_fwd: one launch; the F-channel activations stay in LDS. The middle layer runs on
+ *   v_mfma_f32_16x16x4_f32 (exact f32 products, f32 accumulation).
+ * ocppo_madi_mask_bwd: dw1 .. db3 (shapes of w1 .. b3), the activations recomputed per tile; two
+ *   launches, per-workgroup partial rows added in index order (no atomics: two calls on the same
+ *   inputs are bitwise equal). workspace: ocppo_madi_workspace_bytes(F) = 256 rows of
+ *   (9 F + F + 9 F F + F + 9 F + 1) floats, whatever the number of frames; 4-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+OCPPO_API size_t ocppo_madi_workspace_bytes(int64_t F);
+OCPPO_API int ocppo_madi_mask_fwd(ocppo_stream_t stream, const void* src, int src_dtype,
+                                  const int64_t* idx, int64_t rows, int64_t B, int64_t W,
+                                  int64_t H, int64_t F, const float* w1, const float* b1,
+                                  const float* w2, const float* b2, const float* w3,
+                                  const float* b3, int channels_last, float* out);
+OCPPO_API int ocppo_madi_mask_bwd(ocppo_stream_t stream, const void* src, int src_dtype,
+                                  const int64_t* idx, int64_t rows, int64_t B, int64_t W,
+                                  int64_t H, int64_t F, const float* w1, const float* b1,
+                                  const float* w2, const float* b2, const float* w3,
+                                  const float* b3, int channels_last, const float* g, float* dw1,
+                                  float* db1, float* dw2, float* db2, float* dw3, float* db3,
+                                  void* workspace, size_t workspace_bytes);
 
 #ifdef __cplusplus
 }

@@ -4499,3 +4499,121 @@ def csac_alpha_step(log_prob, temp: SacTemperature, loss=None):
          _check(temp.step, "adam_step", torch.int64, dev, 1), temp.lr, temp.betas[0],
          temp.betas[1], temp.eps, _check(loss, "loss", f, dev, 1))
     return loss
+
+
+# ---------------------------------------------------------------------------------------------
+# MaDi's masker (architectures/madi.py MaskerNet; ppo_atari_madi.py:441, :502): the gather, x / 255,
+# the three padded convolutions, the sigmoid and the multiply as one launch, and the six parameter
+# gradients with the activations recomputed per tile (csrc/ocppo_madi.hip)
+# ---------------------------------------------------------------------------------------------
+MADI_FILTERS = (16, 32)
+# Calls of more stacks than this run the torch modules: 512 stacks of 4 x 84 x 84 is the largest
+# call of either kernel that has run to its end on hardware
+MADI_MAX_STACKS = 512
+# A differentiated call (the update) on the kernels. As single launches at 320 stacks (the
+# script's 10 envs) the fused forward + backward takes 21.6 ms against 16.3 ms for the torch
+# modules with MIOpen free to choose; in the learner, whose torch_deterministic default restricts
+# MIOpen, the update on the torch modules runs at 310 env steps/s and on the kernels at 3,072
+# (tools/exp_madi.py)
+MADI_FUSED_UPDATE = True
+
+
+def madi_ok(src, weights, num_layers: int = 3, padding_mode: str = "zeros", stacks=None,
+            backward: bool = False) -> bool:
+    """The fused masker applies to a call of `stacks` stacks (None: every row of src): three
+    layers, 16 or 32 filters, zero padding, u8 or f32 square frame stacks [rows, W, H, H] and the
+    six masker tensors (w1, b1, w2, b2, w3, b3), all on the GPU, at most MADI_MAX_STACKS stacks;
+    backward: the call is differentiated (MADI_FUSED_UPDATE). Anything else runs the torch
+    modules."""
+    if num_layers != 3 or padding_mode != "zeros" or len(weights) != 6:
+        return False
+    if not isinstance(src, torch.Tensor) or src.device.type != "cuda" or src.dim() != 4 or \
+            src.shape[2] != src.shape[3] or src.dtype not in (torch.uint8, torch.float32) or \
+            min(src.shape) < 1:
+        return False
+    w1, b1, w2, b2, w3, b3 = weights
+    F = w1.shape[0]
+    if F not in MADI_FILTERS:
+        return False
+    shapes = ((F, 1, 3, 3), (F,), (F, F, 3, 3), (F,), (1, F, 3, 3), (1,))
+    if any(t.device != src.device or t.dtype != torch.float32 or tuple(t.shape) != s
+           for t, s in zip(weights, shapes)):
+        return False
+    n = src.shape[0] if stacks is None else stacks
+    return n <= MADI_MAX_STACKS and (MADI_FUSED_UPDATE or not backward)
+
+
+def _madi_args(src, idx, weights, who):
+    if src.dim() != 4 or src.shape[2] != src.shape[3] or src.dtype not in (torch.uint8,
+                                                                            torch.float32):
+        raise ValueError(f"{who}: src must be u8 or f32 [rows, W, H, H], got "
+                         f"{tuple(src.shape)} {src.dtype}")
+    dev = src.device
+    rows, W, H, _ = src.shape
+    w1 = weights[0]
+    F = w1.shape[0]
+    if F not in MADI_FILTERS:
+        raise ValueError(f"{who}: {F} filters (supported: {MADI_FILTERS})")
+    shapes = ((F, 1, 3, 3), (F,), (F, F, 3, 3), (F,), (1, F, 3, 3), (1,))
+    ptrs = []
+    for t, s, n in zip(weights, shapes, ("w1", "b1", "w2", "b2", "w3", "b3")):
+        if tuple(t.shape) != s:
+            raise ValueError(f"{who}: {n} must be {s}, got {tuple(t.shape)}")
+        ptrs.append(_check(t, n, torch.float32, dev))
+    B = rows if idx is None else idx.numel()
+    if min(rows, W, H, B) < 1:
+        raise ValueError(f"{who}: empty input")
+    head = (_stream(dev), _check(src, "src", None, dev), _DTYPE_CODE[src.dtype],
+            _opt(idx, "idx", torch.int64, dev), rows, B, W, H, F, *ptrs)
+    return head, dev, B, W, H, F
+
+
+def _madi_layout(t, B, W, H, dev, name):
+    """channels_last flag of a masked-stack buffer [B, W, H, H] f32 (contiguous or
+    channels_last)."""
+    if t.dtype != torch.float32 or t.device != dev or tuple(t.shape) != (B, W, H, H):
+        raise ValueError(f"{name}: expected f32 {(B, W, H, H)} on {dev}")
+    if t.is_contiguous():
+        return 0
+    if t.is_contiguous(memory_format=torch.channels_last):
+        return 1
+    raise ValueError(f"{name}: must be contiguous or channels_last")
+
+
+def madi_mask(src, idx, weights, out=None, channels_last: bool = False):
+    """MaskerNet.forward of the stacks src[idx] (idx None: every row in order) in one launch:
+    out [B, W, H, H] f32 = x * sigmoid(conv3(relu(conv2(relu(conv1(x / 255)))))), every frame on
+    its own. weights: (w1, b1, w2, b2, w3, b3). out: contiguous or channels_last (made in the
+    format `channels_last` names when None)."""
+    head, dev, B, W, H, F = _madi_args(src, idx, weights, "madi_mask")
+    if out is None:
+        out = torch.empty((B, W, H, H), dtype=torch.float32, device=dev,
+                          memory_format=torch.channels_last if channels_last
+                          else torch.contiguous_format)
+    call("ocppo_madi_mask_fwd", *head, _madi_layout(out, B, W, H, dev, "out"), out.data_ptr())
+    return out
+
+
+def madi_workspace(F: int, device):
+    """The backward's partial rows: ocppo_madi_workspace_bytes(F), the same for any number of
+    frames."""
+    nb = int(_lib.LIB.ocppo_madi_workspace_bytes(F))
+    if nb == 0:
+        raise ValueError(f"madi_workspace: {F} filters (supported: {MADI_FILTERS})")
+    return torch.empty(nb // 4, dtype=torch.float32, device=device)
+
+
+def madi_mask_bwd(src, idx, weights, g, grads=None, workspace=None):
+    """The six parameter gradients of madi_mask for g = dL/d(out) (out's layout). grads: six
+    contiguous f32 tensors of the weights' shapes to write (made when None). Deterministic: two
+    calls on the same inputs are bitwise equal."""
+    head, dev, B, W, H, F = _madi_args(src, idx, weights, "madi_mask_bwd")
+    if grads is None:
+        grads = tuple(torch.empty_like(w, memory_format=torch.contiguous_format) for w in weights)
+    if workspace is None:
+        workspace = _persistent("madi_mask_bwd", dev, F, lambda: madi_workspace(F, dev))
+    gp = [_check(d, f"grads[{i}]", torch.float32, dev, w.numel())
+          for i, (d, w) in enumerate(zip(grads, weights))]
+    call("ocppo_madi_mask_bwd", *head, _madi_layout(g, B, W, H, dev, "g"), g.data_ptr(), *gp,
+         _check(workspace, "workspace", torch.float32, dev), workspace.numel() * 4)
+    return grads

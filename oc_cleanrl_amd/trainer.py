@@ -1394,6 +1394,8 @@ def run(args: Args, device=None, rank: int = 0, world_size: int = 1,
     if rank == 0 and args.save_model:
         torch.save({"model_weights": _own_tensors(tr.agent.state_dict()), "args": asdict(args)},
                    run_dir / f"{args.exp_name}_final.cleanrl_model")
+        if hasattr(tr, "final_extras"):  # a learner's further final files (madi: the masker's)
+            tr.final_extras(run_dir, args.exp_name)
     if rank == 0 and args.eval_episodes > 0:  # ppo_atari_oc.py:687-695 (FinalReward_* summary)
         from .evals import evaluate, make_env
 
