@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCPPO_ABI_VERSION 44
+#define OCPPO_ABI_VERSION 45
 
 /* status codes */
 #define OCPPO_OK 0
@@ -1896,6 +1896,48 @@ OCPPO_API int ocppo_madi_mask_bwd(ocppo_stream_t stream, const void* src, int sr
                                   const float* b3, int channels_last, const float* g, float* dw1,
                                   float* db1, float* dw2, float* db2, float* dw3, float* db3,
                                   void* workspace, size_t workspace_bytes);
+
+/* ---------------------------------------------------------------------------------------------
+ * The IMPALA tower's ConvSequence (cleanrl/qdagger_dqn_atari_impalacnn.py:126-160,
+ * ppg_procgen.py:124-165) as two fused units per direction (ABI 45). Activations are NHWC f32
+ * ([B][H][W][C], torch channels_last), 16-byte aligned; weights are nn.Conv2d's [co][ci][3][3];
+ * every convolution is 3x3, stride 1, zero padding 1, on v_mfma_f32_16x16x4_f32 (exact f32
+ * products, f32 accumulation). Any H, W >= 1. No atomics: two calls on the same inputs are
+ * bitwise equal.
+ * Residual block, C in {16, 32}: y = x + conv1(relu(conv0(relu(x)) + b0)) + b1.
+ *   ocppo_impala_resblock_fwd: one launch. mid (may be NULL): relu(conv0(relu(x)) + b0), [B][H][W][C],
+ *     written for the backward.
+ *   ocppo_impala_resblock_bwd: dx (includes the skip term dy), dw0, db0, dw1, db1 from dy, x, the
+ *     saved mid and the weights; a tile pass and a finish launch.
+ * Convolution + max-pool, cin in 1 .. 4 or {16, 32}, cout in {16, 32}:
+ *   p = max_pool2d(conv(scale x) + b, kernel 3, stride 2, padding 1), [B][(H+1)/2][(W+1)/2][cout].
+ *   ocppo_impala_conv_pool_fwd: one launch. arg (may be NULL): per output element the window
+ *     position 0 .. 8 (row-major) of its maximum, the first one on ties, for the backward.
+ *   ocppo_impala_conv_pool_bwd: dw, db and, when dx is not NULL, dx [B][H][W][cin] (the gradient
+ *     of x, not of scale x) from dp, arg, x and w; a tile pass and a finish launch.
+ * workspace: ocppo_impala_workspace_bytes(cin, cout, resblock) = 256 rows of 2 (9 C C + C)
+ *   (resblock 1, cin == cout == C) or 9 cout cin + cout (resblock 0) floats; 0 for unsupported
+ *   channel counts; 4-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+OCPPO_API size_t ocppo_impala_workspace_bytes(int64_t cin, int64_t cout, int resblock);
+OCPPO_API int ocppo_impala_resblock_fwd(ocppo_stream_t stream, const float* x, int64_t B,
+                                        int64_t H, int64_t W, int64_t C, const float* w0,
+                                        const float* b0, const float* w1, const float* b1,
+                                        float* y, float* mid);
+OCPPO_API int ocppo_impala_resblock_bwd(ocppo_stream_t stream, const float* dy, const float* x,
+                                        const float* mid, int64_t B, int64_t H, int64_t W,
+                                        int64_t C, const float* w0, const float* w1, float* dx,
+                                        float* dw0, float* db0, float* dw1, float* db1,
+                                        void* workspace, size_t workspace_bytes);
+OCPPO_API int ocppo_impala_conv_pool_fwd(ocppo_stream_t stream, const float* x, int64_t B,
+                                         int64_t H, int64_t W, int64_t cin, int64_t cout,
+                                         const float* w, const float* b, float scale, float* out,
+                                         uint8_t* arg);
+OCPPO_API int ocppo_impala_conv_pool_bwd(ocppo_stream_t stream, const float* dp,
+                                         const uint8_t* arg, const float* x, int64_t B, int64_t H,
+                                         int64_t W, int64_t cin, int64_t cout, const float* w,
+                                         float scale, float* dx, float* dw, float* db,
+                                         void* workspace, size_t workspace_bytes);
 
 #ifdef __cplusplus
 }

@@ -1165,6 +1165,9 @@ def fused_trunk(seq: nn.Sequential, x, rows_last: bool = False):
                 and _pair_ok(x, m, mods[i + 2])):
             x = linear2_relu(x, m, mods[i + 2])
             i += 4
+        elif ops.impala_convs(m) is not None and ops.impala_ok(x, *ops.impala_convs(m)):
+            x = ops.impala_sequence(m, x)  # an IMPALA ConvSequence: three fused launches
+            i += 1
         elif _conv_x6_ok(x, m):
             relu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
             x = _conv_x6(x, m, relu)

@@ -4617,3 +4617,171 @@ def madi_mask_bwd(src, idx, weights, g, grads=None, workspace=None):
     call("ocppo_madi_mask_bwd", *head, _madi_layout(g, B, W, H, dev, "g"), g.data_ptr(), *gp,
          _check(workspace, "workspace", torch.float32, dev), workspace.numel() * 4)
     return grads
+
+
+# ---------------------------------------------------------------------------------------------
+# The IMPALA tower's ConvSequence (qdagger_dqn_atari_impalacnn.py:126-160; ppg_procgen.py:124-165)
+# as two fused units: convolution + max-pool and the residual block, forward and backward, 3x3
+# zero-padded convolutions on NHWC f32 (csrc/ocppo_impala.hip)
+# ---------------------------------------------------------------------------------------------
+IMPALA_CHANNELS = (16, 32)
+# The ConvSequences of a network on the fused units (off: the torch modules; tools/exp_impala.py
+# measures both)
+IMPALA_FUSED = True
+
+
+def impala_convs(seq):
+    """The five convolutions of a ppg.ConvSequence (conv, res_block0 / res_block1 with conv0 /
+    conv1), None for any other module: impala_sequence restates that class's forward."""
+    from .ppg import ConvSequence  # ppg imports agents, which imports this module
+
+    if not isinstance(seq, ConvSequence):
+        return None
+    return (seq.conv, seq.res_block0.conv0, seq.res_block0.conv1, seq.res_block1.conv0,
+            seq.res_block1.conv1)
+
+
+def impala_ok(x, *convs) -> bool:
+    """The fused units apply: x a 4-D f32 GPU tensor and every conv a biased 3x3 / stride 1 /
+    zero padding 1 nn.Conv2d on x's device with 16 or 32 output channels and at most 4, 16 or 32
+    input channels. Anything else runs the torch modules."""
+    if not (IMPALA_FUSED and isinstance(x, torch.Tensor) and x.is_cuda
+            and x.dtype == torch.float32 and x.dim() == 4 and min(x.shape) >= 1 and convs):
+        return False
+    for m in convs:
+        if not (isinstance(m, torch.nn.Conv2d) and m.kernel_size == (3, 3) and m.stride == (1, 1)
+                and m.padding == (1, 1) and m.dilation == (1, 1) and m.groups == 1
+                and m.padding_mode == "zeros" and m.bias is not None
+                and m.weight.device == x.device and m.weight.dtype == torch.float32
+                and m.out_channels in IMPALA_CHANNELS
+                and (m.in_channels <= 4 or m.in_channels in IMPALA_CHANNELS)):
+            return False
+    return True
+
+
+def _nhwc(t, name: str):
+    """[B, H, W, C] contiguous view of a 4-D f32 tensor (a copy unless it is channels_last)."""
+    if t.dim() != 4 or t.dtype != torch.float32:
+        raise ValueError(f"{name}: expected a 4-D f32 tensor, got {tuple(t.shape)} {t.dtype}")
+    return t.contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1)
+
+
+def impala_workspace(cin: int, cout: int, resblock: bool, device):
+    """A backward's partial rows: ocppo_impala_workspace_bytes, the same for any batch."""
+    nb = int(_lib.LIB.ocppo_impala_workspace_bytes(cin, cout, int(resblock)))
+    if nb == 0:
+        raise ValueError(f"impala_workspace: {cin} -> {cout} channels are not supported")
+    return torch.empty(nb // 4, dtype=torch.float32, device=device)
+
+
+class _ImpalaResblock(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w0, b0, w1, b1, need: bool):
+        xh = _nhwc(x, "x")
+        B, H, W, C = xh.shape
+        dev = xh.device
+        w0, w1 = w0.contiguous(), w1.contiguous()
+        if C not in IMPALA_CHANNELS or tuple(w0.shape) != (C, C, 3, 3) or w0.shape != w1.shape:
+            raise ValueError(f"impala_resblock: x {tuple(x.shape)} with weights {tuple(w0.shape)} "
+                             f"/ {tuple(w1.shape)} (C -> C 3x3, C in {IMPALA_CHANNELS})")
+        y = torch.empty_like(xh)
+        mid = torch.empty_like(xh) if need else None
+        call("ocppo_impala_resblock_fwd", _stream(dev), _check(xh, "x", torch.float32, dev), B, H,
+             W, C, _check(w0, "w0", torch.float32, dev), _check(b0, "b0", torch.float32, dev, C),
+             _check(w1, "w1", torch.float32, dev), _check(b1, "b1", torch.float32, dev, C),
+             y.data_ptr(), _opt(mid, "mid", torch.float32, dev))
+        if need:
+            ctx.save_for_backward(xh, mid, w0, w1)
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, dy):
+        xh, mid, w0, w1 = ctx.saved_tensors
+        B, H, W, C = xh.shape
+        dev = xh.device
+        dyh = _nhwc(dy, "dy")
+        dx = torch.empty_like(xh)
+        dw0, dw1 = torch.empty_like(w0), torch.empty_like(w1)
+        db0, db1 = (torch.empty(C, dtype=torch.float32, device=dev) for _ in range(2))
+        ws = _persistent("impala_resblock_bwd", dev, C, lambda: impala_workspace(C, C, True, dev))
+        call("ocppo_impala_resblock_bwd", _stream(dev), _check(dyh, "dy", torch.float32, dev,
+                                                               xh.numel()),
+             xh.data_ptr(), mid.data_ptr(), B, H, W, C, w0.data_ptr(), w1.data_ptr(),
+             dx.data_ptr(), dw0.data_ptr(), db0.data_ptr(), dw1.data_ptr(), db1.data_ptr(),
+             ws.data_ptr(), ws.numel() * 4)
+        return dx.permute(0, 3, 1, 2), dw0, db0, dw1, db1, None
+
+
+def impala_resblock(x, w0, b0, w1, b1):
+    """x + conv1(relu(conv0(relu(x)) + b0)) + b1 for x [B, C, H, W] f32 (channels_last, or
+    copied to it), both convolutions 3x3 zero-padded C -> C, C 16 or 32: one launch, the result
+    channels_last. Differentiable in x and the four parameters (a tile pass + a finish launch; the
+    mid activation is saved when any of them requires a gradient); deterministic."""
+    need = torch.is_grad_enabled() and any(t.requires_grad for t in (x, w0, b0, w1, b1))
+    return _ImpalaResblock.apply(x, w0, b0, w1, b1, need)
+
+
+class _ImpalaConvPool(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b, scale: float, need: bool, need_dx: bool):
+        xh = _nhwc(x, "x")
+        B, H, W, cin = xh.shape
+        dev = xh.device
+        w = w.contiguous()
+        cout = w.shape[0]
+        if tuple(w.shape) != (cout, cin, 3, 3):
+            raise ValueError(f"impala_conv_pool: x {tuple(x.shape)} with weight {tuple(w.shape)}")
+        out = torch.empty((B, (H + 1) // 2, (W + 1) // 2, cout), dtype=torch.float32, device=dev)
+        arg = torch.empty(out.shape, dtype=torch.uint8, device=dev) if need else None
+        call("ocppo_impala_conv_pool_fwd", _stream(dev), _check(xh, "x", torch.float32, dev), B, H,
+             W, cin, cout, _check(w, "w", torch.float32, dev),
+             _check(b, "b", torch.float32, dev, cout), scale, out.data_ptr(),
+             _opt(arg, "arg", torch.uint8, dev))
+        if need:
+            ctx.save_for_backward(xh, arg, w)
+            ctx.scale, ctx.need_dx = scale, need_dx
+        return out.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, dp):
+        xh, arg, w = ctx.saved_tensors
+        B, H, W, cin = xh.shape
+        cout, dev = w.shape[0], xh.device
+        dph = _nhwc(dp, "dp")
+        dx = torch.empty_like(xh) if ctx.need_dx else None
+        dw = torch.empty_like(w)
+        db = torch.empty(cout, dtype=torch.float32, device=dev)
+        ws = _persistent("impala_conv_pool_bwd", dev, (cin, cout),
+                         lambda: impala_workspace(cin, cout, False, dev))
+        call("ocppo_impala_conv_pool_bwd", _stream(dev),
+             _check(dph, "dp", torch.float32, dev, arg.numel()), arg.data_ptr(), xh.data_ptr(), B,
+             H, W, cin, cout, w.data_ptr(), ctx.scale, _opt(dx, "dx", torch.float32, dev),
+             dw.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel() * 4)
+        return None if dx is None else dx.permute(0, 3, 1, 2), dw, db, None, None, None
+
+
+def impala_conv_pool(x, w, b, scale: float = 1.0):
+    """max_pool2d(conv2d(x * scale, w, b, padding=1), 3, stride 2, padding 1) for x [B, Cin, H, W]
+    f32 (channels_last, or copied to it), Cin <= 4, 16 or 32, 16 or 32 output channels: one launch,
+    the result [B, Cout, ceil(H / 2), ceil(W / 2)] channels_last. The scale is one f32
+    multiplication per element (1 / 255 folds a pixel network's x / 255 in). Differentiable in
+    the parameters and, when it requires a gradient, in x; deterministic; pool ties go to the
+    first window position, as torch's."""
+    if not scale > 0:
+        raise ValueError(f"impala_conv_pool: scale {scale} must be > 0")
+    grad = torch.is_grad_enabled()
+    need_dx = grad and x.requires_grad
+    need = need_dx or (grad and (w.requires_grad or b.requires_grad))
+    return _ImpalaConvPool.apply(x, w, b, float(scale), need, need_dx)
+
+
+def impala_sequence(seq, x, scale: float = 1.0):
+    """A ConvSequence's forward (conv, max-pool, two residual blocks) on the fused units: three
+    launches, and three tile passes + three finish launches backward."""
+    convs = impala_convs(seq)
+    if convs is None:
+        raise TypeError(f"impala_sequence: expected a ppg.ConvSequence, got {type(seq).__name__}")
+    conv, r0a, r0b, r1a, r1b = convs
+    x = impala_conv_pool(x, conv.weight, conv.bias, scale)
+    x = impala_resblock(x, r0a.weight, r0a.bias, r0b.weight, r0b.bias)
+    return impala_resblock(x, r1a.weight, r1a.bias, r1b.weight, r1b.bias)

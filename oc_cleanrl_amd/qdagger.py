@@ -24,8 +24,8 @@ launches as the student's acting.
 
 Declared differences from the script: no hub download, `teacher_model_path` names a
 local file; a teacher mean return of 0 (or a non-finite one) is refused, the script would divide
-by it; the IMPALA student has its modules here but no kernels, the trainer refuses it; more than
-one env is allowed (the ring takes finished episodes in ascending env order); steps are counted
+by it; the IMPALA student (student_network impala) reads pixel stacks, so the trainer refuses it
+with obs_mode obj; more than one env is allowed (the ring takes finished episodes in ascending env order); steps are counted
 as DQNTrainer counts them (the count after the step), with the script's offset added.
 """
 from __future__ import annotations
@@ -40,7 +40,8 @@ import torch.nn as nn
 
 from . import evals, ops
 from .args import ACTION_COUNTS
-from .dqn import DQNArgs, DQNTrainer, learner_main, make_qnet, run_learner
+from .agents import Predictor, fused_trunk, q_head
+from .dqn import DQNArgs, DQNTrainer, QNetwork, learner_main, make_qnet, run_learner
 
 TEACHER_EVAL_EPSILON = 0.05  # :266
 
@@ -98,7 +99,7 @@ class QDaggerArgs:
     # [oc_cleanrl_amd] QDagger's own
     teacher_model_path: str = ""  # a .cleanrl_model payload of this package or a bare state dict
     teacher_return: Optional[float] = None  # set: skip the teacher evaluation and use this mean
-    student_network: str = "auto"  # auto (dqn.make_qnet) | impala (the script's; no kernels yet)
+    student_network: str = "auto"  # auto (dqn.make_qnet) | impala (the script's; obs_mode dqn)
 
 
 # ---- the script's own student (:126-184): modules, keys and default init -----------------------
@@ -114,10 +115,11 @@ def impala_sequence(input_shape, out_channels: int) -> nn.Module:
     return seq
 
 
-class QNetworkImpala(nn.Module):
+class QNetworkImpala(Predictor):
     """QNetwork of :164-184: three ConvSequences (16, 32, 32), Flatten, ReLU, Linear 256, ReLU,
-    Linear A; forward = network(x / 255). Modules, state-dict keys and init only: the 3x3 pad-1
-    residual convolutions and the max-pool have no HIP kernels, so QDaggerTrainer refuses it."""
+    Linear A; forward = network(x / 255) on the modules. q_values runs each ConvSequence as three
+    fused launches (ops.impala_sequence, where ops.impala_ok holds; the modules otherwise) with
+    the / 255 folded into the first one, the Linear 256 + ReLU and the head as dqn.QNetwork's."""
 
     def __init__(self, obs_shape, n_actions):
         super().__init__()
@@ -132,6 +134,18 @@ class QNetworkImpala(nn.Module):
 
     def forward(self, x):
         return self.network(x / 255.0)
+
+    def q_values(self, x):
+        net = self.network
+        if ops.impala_ok(x, *ops.impala_convs(net[0])):
+            # x / 255 rides in the first conv + pool launch (one f32 multiplication per element)
+            h = fused_trunk(net[1:-1], ops.impala_sequence(net[0], x, scale=1.0 / 255.0))
+        else:
+            h = fused_trunk(net[:-1], x / 255.0)
+        return q_head(h, net[-1])
+
+    get_action_and_value = QNetwork.get_action_and_value
+    predict = QNetwork.predict
 
 
 def linear_schedule(start_e: float, end_e: float, duration: float, t: int) -> float:
@@ -197,13 +211,13 @@ class QDaggerTrainer(DQNTrainer):
 
     def __init__(self, args: QDaggerArgs, device, log: bool = True):
         a = args
-        if a.student_network == "impala":
-            raise NotImplementedError(
-                "student_network impala: the script's IMPALA student has its modules here "
-                "(qdagger.QNetworkImpala) but no HIP kernels: the 3x3 pad-1 residual convolutions "
-                "and the max-pool are missing; use student_network auto")
-        if a.student_network != "auto":
+        if a.student_network not in ("auto", "impala"):
             raise ValueError(f"student_network {a.student_network!r}: auto or impala")
+        if a.student_network == "impala" and a.obs_mode != "dqn":
+            raise NotImplementedError(
+                "student_network impala: the script's IMPALA student (qdagger.QNetworkImpala), its "
+                "3x3 pad-1 residual convolutions and the max-pool read pixel stacks: use "
+                "--obs-mode dqn")
         if a.num_envs < 1 or a.teacher_steps < 1 or a.offline_steps < 0:
             raise ValueError("need num_envs >= 1, teacher_steps >= 1 and offline_steps >= 0")
         if not a.temperature > 0:
@@ -237,6 +251,12 @@ class QDaggerTrainer(DQNTrainer):
         self.step_record = None  # a list: the eager path appends (env.reward, env.done) per step
 
     # ---- DQNTrainer's hooks ------------------------------------------------------------------
+    def _make_net(self) -> nn.Module:
+        """The student and its target: the script's IMPALA network or dqn.make_qnet's."""
+        if self.args.student_network == "impala":
+            return QNetworkImpala(self.obs_shape, self.A)
+        return super()._make_net()
+
     def _actor(self) -> nn.Module:
         return self._acting if self._acting is not None else self.q
 
