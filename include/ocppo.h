@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCPPO_ABI_VERSION 45
+#define OCPPO_ABI_VERSION 46
 
 /* status codes */
 #define OCPPO_OK 0
@@ -1938,6 +1938,43 @@ OCPPO_API int ocppo_impala_conv_pool_bwd(ocppo_stream_t stream, const float* dp,
                                          int64_t W, int64_t cin, int64_t cout, const float* w,
                                          float scale, float* dx, float* dw, float* db,
                                          void* workspace, size_t workspace_bytes);
+
+/* ---------------------------------------------------------------------------------------------
+ * LayerNorm over [C, H, W] + ReLU (the pixel QNetwork of cleanrl/pqn_atari_envpool.py:119-131),
+ * ABI 46. All f32. R rows of E = C HW contiguous floats, 1 <= E <= OCPPO_LN_CHW_MAX_E, any R >= 0
+ * (R = 0 launches nothing and returns OCPPO_OK), any C >= 1 and HW >= 1. gamma, beta, dgamma and
+ * dbeta are always in [C, H, W] order (parameter index c HW + p). channels_last = 0: the rows are
+ * NCHW (memory index m <-> parameter index m); channels_last != 0: the rows are NHWC
+ * (m = p C + c <-> parameter index c HW + p); the map is applied inside the kernels, the
+ * parameters are read once per workgroup. E % 4 == 0 with every row pointer 16-byte aligned
+ * takes 16-byte accesses, anything else a scalar path with the same arithmetic. A size outside
+ * the contract or a null required pointer returns OCPPO_E_INVALID before any launch. No atomics:
+ * two runs are bitwise equal. Graph-capturable.
+ *
+ * ocppo_ln_chw_relu_fwd: y = relu(LayerNorm(x) * gamma + beta) per row (relu = 0: no ReLU);
+ * mean, rstd [R] are written. One workgroup holds one row on chip: x is read once. The row is
+ * centred on a first mean, re-centred once, and the variance is the mean of the squared
+ * deviations (ocppo_ln_relu_fwd's arithmetic); rstd = 1 / sqrt(var + eps).
+ * ocppo_ln_chw_relu_bwd: dx [R, E] in the rows' layout, dgamma, dbeta [E] from dy, x, y (the ReLU
+ * mask is y > 0; y may be NULL with relu = 0), mean and rstd; dy, x and y are read once each.
+ * min(R, OCPPO_LN_CHW_MAX_PARTS) workgroups (a function of R alone) each store one dgamma / dbeta
+ * partial [2][E], summed over their rows in row order, to the workspace
+ * (ocppo_ln_chw_workspace_bytes(R, E); 0 outside the contract; a shorter or NULL buffer returns
+ * OCPPO_E_WORKSPACE) with plain stores; a second launch of the same call sums the partials in
+ * workgroup order (eight consecutive segments, each in order, then the segments in order).
+ * ------------------------------------------------------------------------------------------- */
+#define OCPPO_LN_CHW_MAX_E 16384
+#define OCPPO_LN_CHW_MAX_PARTS 256
+OCPPO_API int ocppo_ln_chw_relu_fwd(ocppo_stream_t stream, const float* x, const float* gamma,
+                                    const float* beta, int64_t R, int64_t C, int64_t HW,
+                                    int channels_last, double eps, int relu, float* y,
+                                    float* mean, float* rstd);
+OCPPO_API size_t ocppo_ln_chw_workspace_bytes(int64_t R, int64_t E);
+OCPPO_API int ocppo_ln_chw_relu_bwd(ocppo_stream_t stream, const float* dy, const float* x,
+                                    const float* y, const float* gamma, const float* mean,
+                                    const float* rstd, int64_t R, int64_t C, int64_t HW,
+                                    int channels_last, int relu, float* dx, float* dgamma,
+                                    float* dbeta, void* workspace, size_t workspace_bytes);
 
 #ifdef __cplusplus
 }

@@ -3240,6 +3240,112 @@ def ln_relu(x, weight, bias, eps: float = 1e-5, relu: bool = True):
     return _LnRelu.apply(x, weight, bias, eps, relu)
 
 
+LN_CHW_MAX_E, LN_CHW_MAX_PARTS = _lib.OCPPO_LN_CHW_MAX_E, _lib.OCPPO_LN_CHW_MAX_PARTS
+
+
+def _chw_format(x):
+    """channels_last flag of a dense 4-D tensor's memory (read from its strides; NCHW wins where
+    both hold, the two index maps being one there), None when it is neither."""
+    if x.dim() != 4:
+        return None
+    if x.is_contiguous():
+        return False
+    return True if x.is_contiguous(memory_format=torch.channels_last) else None
+
+
+def ln_chw_ok(x, ln) -> bool:
+    """ln_chw_relu applies: an affine nn.LayerNorm over exactly the [C, H, W] of a GPU f32
+    [B, C, H, W] tensor, dense in NCHW or channels_last memory, C H W <= 16384."""
+    return (isinstance(ln, torch.nn.LayerNorm) and ln.elementwise_affine and ln.bias is not None
+            and isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32
+            and _chw_format(x) is not None and tuple(ln.normalized_shape) == tuple(x.shape[1:])
+            and 1 <= x[0].numel() <= LN_CHW_MAX_E)
+
+
+def _ln_chw_shape(x, weight, who: str):
+    """(R, C, HW, channels_last) of a [B, C, H, W] tensor and its [C, H, W] parameters."""
+    cl = _chw_format(x)
+    if cl is None or x.shape[0] == 0 or weight.numel() != x[0].numel() or \
+            not 1 <= weight.numel() <= LN_CHW_MAX_E:
+        raise ValueError(f"{who}: x {tuple(x.shape)} strides {tuple(x.stride())}, weight "
+                         f"{tuple(weight.shape)} (a dense NCHW or channels_last [B, C, H, W] "
+                         f"tensor, one weight per element of [C, H, W], C H W <= {LN_CHW_MAX_E})")
+    return x.shape[0], x.shape[1], x.shape[2] * x.shape[3], int(cl)
+
+
+def _same_format(t, x, cl: int, name: str, dev):
+    """data pointer of f32 `t`, which must have x's shape and memory format"""
+    fmt = torch.channels_last if cl else torch.contiguous_format
+    if t.shape != x.shape or not t.is_contiguous(memory_format=fmt) or \
+            t.dtype != torch.float32 or t.device != dev:
+        raise ValueError(f"{name}: must be float32 on {dev} with x's shape and memory format")
+    return t.data_ptr()
+
+
+def ln_chw_relu_fwd(x, weight, bias, eps: float = 1e-5, relu: bool = True):
+    """relu(LayerNorm_[C,H,W](x) * weight + bias) per sample of x [B, C, H, W] (relu=False: plain
+    LayerNorm) -> (y in x's memory format, mean [B], rstd [B]). weight / bias stay in the
+    module's [C, H, W] order whatever x's format: the kernel maps the index."""
+    R, C, HW, cl = _ln_chw_shape(x, weight, "ln_chw_relu_fwd")
+    dev, f = x.device, torch.float32
+    y = torch.empty_like(x)  # preserves a dense tensor's strides
+    mean = torch.empty(R, dtype=f, device=dev)
+    rstd = torch.empty(R, dtype=f, device=dev)
+    call("ocppo_ln_chw_relu_fwd", _stream(dev), _same_format(x, x, cl, "x", dev),
+         _check(weight, "weight", f, dev, C * HW), _check(bias, "bias", f, dev, C * HW), R, C, HW,
+         cl, float(eps), int(bool(relu)), _same_format(y, x, cl, "y", dev), mean.data_ptr(),
+         rstd.data_ptr())
+    return y, mean, rstd
+
+
+def ln_chw_relu_bwd(dy, x, y, weight, mean, rstd, relu: bool = True):
+    """(dx in x's memory format, dweight, dbias as weight) of ln_chw_relu_fwd; dy (and y, read
+    only with relu) in x's format. The partials live in one buffer per size (_persistent): every
+    call writes all the partials it reads."""
+    R, C, HW, cl = _ln_chw_shape(x, weight, "ln_chw_relu_bwd")
+    dev, f = x.device, torch.float32
+    dx = torch.empty_like(x)
+    dw, db = torch.empty_like(weight), torch.empty_like(weight)
+    nb = int(_lib.LIB.ocppo_ln_chw_workspace_bytes(R, C * HW))
+    ws = _persistent("ln_chw_relu_bwd", dev, nb, lambda: torch.empty(
+        max(nb // 4, 1), dtype=f, device=dev))
+    call("ocppo_ln_chw_relu_bwd", _stream(dev), _same_format(dy, x, cl, "dy", dev),
+         _same_format(x, x, cl, "x", dev), _same_format(y, x, cl, "y", dev) if relu else None,
+         _check(weight, "weight", f, dev, C * HW), _check(mean, "mean", f, dev, R),
+         _check(rstd, "rstd", f, dev, R), R, C, HW, cl, int(bool(relu)),
+         _same_format(dx, x, cl, "dx", dev), _check(dw, "dweight", f, dev),
+         _check(db, "dbias", f, dev),
+         ws.data_ptr(), nb)
+    return dx, dw, db
+
+
+class _LnChwRelu(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps: float, relu: bool):
+        x, w = x.detach(), weight.detach()
+        y, mean, rstd = ln_chw_relu_fwd(x, w, bias.detach(), eps, relu)
+        ctx.save_for_backward(x, y, w, mean, rstd)
+        ctx.relu = relu
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y, w, mean, rstd = ctx.saved_tensors
+        # the gradient in the activation's memory format
+        g = g.contiguous(memory_format=torch.channels_last if _chw_format(x) else
+                         torch.contiguous_format)
+        dx, dw, db = timed("ln_chw_relu_bwd", lambda: ln_chw_relu_bwd(g, x, y, w, mean, rstd,
+                                                                      ctx.relu))
+        return dx, dw, db, None, None
+
+
+def ln_chw_relu(x, weight, bias, eps: float = 1e-5, relu: bool = True):
+    """Differentiable relu(LayerNorm_[C,H,W](x) * weight + bias) of a [B, C, H, W] tensor in
+    either memory format: the LayerNorm -> ReLU after every convolution of pqn_atari_envpool.py's
+    QNetwork as one launch (two in the backward). y and dx come back in x's format."""
+    return _LnChwRelu.apply(x, weight, bias, eps, relu)
+
+
 def pqn_act_ok(hidden, wq) -> bool:
     """pqn_act applies: GPU f32 [N, H] rows and an [A, H] head with A <= 18, H a multiple of 4 up
     to 1024, both contiguous and 16-B aligned (q_head_epsilon_greedy's contract, widened)."""

@@ -12,7 +12,10 @@ rollout buffer, captured rollout, minibatch staging, flat parameter buffer and h
   * a minibatch is trunk -> Q head -> ops.pqn_loss_fwd_bwd -> backward, then ops.FlatRAdam;
   * every `Linear -> LayerNorm -> ReLU` on 2-D rows is agents.linear_act (no ReLU) + ops.ln_relu
     in the rollout; in the update the LayerNorm + ReLU stay on torch unless FUSED_LN_UPDATE (the
-    kernel pair measured slower than torch's there).
+    kernel pair measured slower than torch's there);
+  * every `Conv2d -> LayerNorm([C, H, W]) -> ReLU` of the pixel network is the convolution
+    (agents' ops.conv_x6 route without its ReLU where that route's gate holds, else the module)
+    + ops.ln_chw_relu in the rollout, and in the update under FUSED_LN_CHW_UPDATE.
 `FUSED_PQN = False` selects torch's F.layer_norm / relu, torch's argmax for the greedy value,
 F.mse_loss and torch.optim.RAdam instead (the exploration draw stays ops.epsilon_greedy: the
 package's one stream, so both paths act alike from one seed).
@@ -20,7 +23,7 @@ package's one stream, so both paths act alike from one seed).
 Declared differences from the script: no envpool / ALE here (--backend Synthetic, the package's
 device envs); `architecture` / `obs_mode` pick the network ("PQN_OBJ", the default: the PPObj
 encoder / decoder on object vectors with a LayerNorm before every ReLU; "PQN": the script's
-QNetwork on pixels, whose LayerNorms over [C, H, W] stay on torch); exploration is
+QNetwork on pixels); exploration is
 ocppo_epsilon_greedy's law (one coin per global step for the whole vector of envs, the
 counter-based stream), not torch.rand per env; one GPU.
 """
@@ -34,7 +37,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .agents import EnvSpec, Predictor, layer_init, linear_act, object_trunk
+from .agents import (EnvSpec, Predictor, _conv_x6, _conv_x6_ok, layer_init, linear_act,
+                     object_trunk)
 from .args import CORE_FIXED, CORE_SKIP, learner_args, single_gpu_sizes
 from .trainer import PPOTrainer, learner_main, run
 
@@ -47,6 +51,13 @@ FUSED_PQN = True
 # 42.5 vs 28.5 at [4096, 128] (tools/pqn_rate.py) -- so the update's LayerNorms run on
 # torch; the rollout's rows (3.1 vs 5.4 us) run on the kernel
 FUSED_LN_UPDATE = False
+# ops.ln_chw_relu (the pixel network's LayerNorm([C, H, W]) + ReLU) also under autograd. The
+# rollout's rows always run on the kernel; the update's do when this is on. On: at the script's
+# minibatch of 256 rows the kernel pair beat torch's layer_norm + relu with autograd in both runs
+# at all three widths -- 68.0 / 68.2 vs 145.1 / 147.2 us at [256, 32, 20, 20], 31.6 / 31.5 vs
+# 70.7 / 70.7 at [256, 64, 9, 9], 21.7 / 21.7 vs 53.4 / 53.6 at [256, 64, 7, 7]
+# (tools/ln_chw_rate.py)
+FUSED_LN_CHW_UPDATE = True
 
 ARCHITECTURES = ("PQN_OBJ", "PQN")
 
@@ -119,6 +130,19 @@ def _fusable_norm(x, ln) -> bool:
             (FUSED_LN_UPDATE or not torch.is_grad_enabled()))
 
 
+def _fusable_norm_chw(x, ln) -> bool:
+    """LayerNorm([C, H, W]) [-> ReLU] on a GPU f32 [B, C, H, W] tensor that ops.ln_chw_relu
+    takes: the rollout's (no autograd), and the update's with FUSED_LN_CHW_UPDATE."""
+    return (FUSED_PQN and ops.ln_chw_ok(x, ln) and
+            (FUSED_LN_CHW_UPDATE or not torch.is_grad_enabled()))
+
+
+def _fusable_conv(x, conv, after) -> bool:
+    """A convolution in front of a LayerNorm that agents' ops.conv_x6 route takes (its own gate:
+    channels_last operands, tile-divisible rows)."""
+    return FUSED_PQN and isinstance(after, nn.LayerNorm) and _conv_x6_ok(x, conv)
+
+
 def trunk_layers(envs, pixels: bool, encoder_dims=(128, 64), decoder_dims=(128,)):
     """(modules, output width) of the network below the Q head, made in the script's order
     (:119-134): the pixel stack, or the PPObj encoder / decoder (agents.object_trunk) with a
@@ -146,12 +170,22 @@ def trunk_layers(envs, pixels: bool, encoder_dims=(128, 64), decoder_dims=(128,)
 
 def run_trunk(mods, x):
     """The modules below the Q head on x: a fusable Linear is agents.linear_act, a fusable
-    LayerNorm [-> ReLU] one ops.ln_relu launch, anything else the module itself."""
+    LayerNorm [-> ReLU] one ops.ln_relu launch (ops.ln_chw_relu over [C, H, W], in the memory
+    format x arrives in), a fusable convolution in front of a LayerNorm agents' ops.conv_x6
+    route without a ReLU, anything else the module itself (nn.Flatten reads logical NCHW order
+    whatever the memory format)."""
     i = 0
     while i < len(mods):
         m = mods[i]
         if _fusable_linear(x, m):
             x = linear_act(x, m, False)
+        elif _fusable_norm_chw(x, m):
+            relu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
+            x = ops.timed("ln_chw_relu", lambda h=x, ln=m, relu=relu: ops.ln_chw_relu(
+                h, ln.weight, ln.bias, ln.eps, relu))
+            i += 1 if relu else 0
+        elif _fusable_conv(x, m, mods[i + 1] if i + 1 < len(mods) else None):
+            x = _conv_x6(x, m, False)
         elif _fusable_norm(x, m):
             relu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
             x = ops.timed("ln_relu", lambda h=x, ln=m, relu=relu: ops.ln_relu(
