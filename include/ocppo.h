@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCPPO_ABI_VERSION 46
+#define OCPPO_ABI_VERSION 47
 
 /* status codes */
 #define OCPPO_OK 0
@@ -1975,6 +1975,53 @@ OCPPO_API int ocppo_ln_chw_relu_bwd(ocppo_stream_t stream, const float* dy, cons
                                     const float* rstd, int64_t R, int64_t C, int64_t HW,
                                     int channels_last, int relu, float* dx, float* dgamma,
                                     float* dbeta, void* workspace, size_t workspace_bytes);
+
+/* ---------------------------------------------------------------------------------------------
+ * The pixel RND body (cleanrl/ppo_rnd_envpool.py:193-219), ABI 47: Conv2d(1, 32, 8, 4) ->
+ * Conv2d(32, 64, 4, 2) -> Conv2d(64, 64, 3, 1), LeakyReLU(0.01) after each, nn.Flatten, on the
+ * normalised newest frame. The geometry is fixed: H = W = 84, c1 / c2 / c3 = 32 / 64 / 64; anything
+ * else, a null required pointer or a misaligned one returns OCPPO_E_INVALID before any launch.
+ * All products on v_mfma_f32_16x16x4_f32 (exact f32 products, f32 accumulation). No atomics: two
+ * runs are bitwise equal. Graph-capturable (device scalars only).
+ *
+ * Frames: image r is the 7056 bytes at frames + (idx ? idx[r] : r) * row_stride (u8; frames and
+ * row_stride multiples of 4: the newest frame of [.., 4, 84, 84] stacks, addressed through a
+ * minibatch's row indices). A row index outside [0, src_rows) reads nothing; that image's outputs
+ * are NaN. state: the f64 running statistics [2 * 7056 + 1] of ocppo_rms_update; the input of
+ * the first layer is f32(clip((f64(x) - mean) / sqrt(var), -5, 5)), ocppo_rnd_normalize's
+ * arithmetic, computed on chip (no normalised frame is stored).
+ * Weights are nn.Conv2d's [Cout][Cin][KH][KW], 4-byte aligned, read in place.
+ *
+ * ocppo_rnd_body_fwd: one launch, one workgroup per image. out [R, 3136] in nn.Flatten's NCHW
+ * order from (w1 .. b3); with the second set (tw1 .. tb3 and tout all given, or all NULL) tout
+ * [R, 3136] from the same on-chip frame. a1 [R, 32 * 400] and a2 [R, 64 * 81] (both or neither;
+ * channel-major, a1 16-byte aligned): the first set's activations, for the backward.
+ * ocppo_rnd_body_bwd: dw1 [32, 64], db1, dw2 [64, 512], db2, dw3 [64, 576], db3 of the first set
+ * from dout [R, 3136], a1, a2 and a3 (the forward's out); there is no input gradient. Three
+ * launches: the per-image data-gradient chain (dz3, dz2, dz1 -> workspace), the weight-gradient
+ * products over chunks of OCPPO_RND_BODY_CHUNK images (register accumulators, one plainly stored
+ * partial row per chunk; bias gradients summed in f64), and the finish that adds the partial rows
+ * in chunk order. workspace: ocppo_rnd_body_workspace_bytes(R) (0 outside 1 <= R <= 2^20),
+ * 16-byte aligned, no initial contents needed; a shorter one returns OCPPO_E_WORKSPACE.
+ * ------------------------------------------------------------------------------------------- */
+#define OCPPO_RND_BODY_CHUNK 16
+OCPPO_API int ocppo_rnd_body_fwd(ocppo_stream_t stream, const uint8_t* frames, int64_t src_rows,
+                                 int64_t row_stride, const int64_t* idx, int64_t R, int64_t H,
+                                 int64_t W, int64_t c1, int64_t c2, int64_t c3,
+                                 const double* state, const float* w1, const float* b1,
+                                 const float* w2, const float* b2, const float* w3,
+                                 const float* b3, const float* tw1, const float* tb1,
+                                 const float* tw2, const float* tb2, const float* tw3,
+                                 const float* tb3, float* out, float* tout, float* a1, float* a2);
+OCPPO_API size_t ocppo_rnd_body_workspace_bytes(int64_t R);
+OCPPO_API int ocppo_rnd_body_bwd(ocppo_stream_t stream, const uint8_t* frames, int64_t src_rows,
+                                 int64_t row_stride, const int64_t* idx, int64_t R, int64_t H,
+                                 int64_t W, int64_t c1, int64_t c2, int64_t c3,
+                                 const double* state, const float* a1, const float* a2,
+                                 const float* a3, const float* w2, const float* w3,
+                                 const float* dout, float* dw1, float* db1, float* dw2,
+                                 float* db2, float* dw3, float* db3, void* workspace,
+                                 size_t workspace_bytes);
 
 #ifdef __cplusplus
 }

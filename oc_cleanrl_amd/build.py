@@ -43,10 +43,12 @@ HIP_FLAGS = [
 # on gfx950 parts without raising an error, and the file's VALU work is bias / ReLU / skip
 # epilogues beside MFMAs, where packing would gain nothing measurable (no speed figure is claimed).
 # ocppo_ln_chw.hip: the same guard; its kernels are bound by memory traffic, not by VALU issue.
+# ocppo_rnd_body.hip: the same guard; bias / LeakyReLU epilogues beside MFMAs.
 NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 FILE_FLAGS = {"ocppo_gemm.hip": ["-fno-slp-vectorize"],
               "ocppo_impala.hip": NO_PACKED_F32,
-              "ocppo_ln_chw.hip": NO_PACKED_F32}
+              "ocppo_ln_chw.hip": NO_PACKED_F32,
+              "ocppo_rnd_body.hip": NO_PACKED_F32}
 
 
 def sources() -> list[Path]:

@@ -4891,3 +4891,125 @@ def impala_sequence(seq, x, scale: float = 1.0):
     x = impala_conv_pool(x, conv.weight, conv.bias, scale)
     x = impala_resblock(x, r0a.weight, r0a.bias, r0b.weight, r0b.bias)
     return impala_resblock(x, r1a.weight, r1a.bias, r1b.weight, r1b.bias)
+
+
+# ---------------------------------------------------------------------------------------------
+# The pixel RND body (ppo_rnd_envpool.py:193-219): three LeakyReLU convolutions + Flatten on the
+# normalised newest frame, fused per image, straight from the u8 frames and the f64 statistics
+# (csrc/ocppo_rnd_body.hip)
+# ---------------------------------------------------------------------------------------------
+RND_BODY_CHUNK = _lib.OCPPO_RND_BODY_CHUNK
+RND_BODY_FRAME = 84 * 84
+RND_BODY_FEATURES = 64 * 7 * 7
+_RND_BODY_GEOMETRY = ((1, 32, 8, 4), (32, 64, 4, 2), (64, 64, 3, 1))  # cin, cout, kernel, stride
+
+
+def rnd_body_convs(seq):
+    """The three convolutions of a pixel RND network (rnd.RNDModel's predictor / target: Conv2d,
+    LeakyReLU, Conv2d, LeakyReLU, Conv2d, LeakyReLU, Flatten, ...)."""
+    return seq[0], seq[2], seq[4]
+
+
+def rnd_body_ok(frames, state, convs) -> bool:
+    """The fused body applies: frames a GPU u8 [rows, 7056] tensor whose rows are contiguous and a
+    multiple of 4 bytes apart (the newest frame of [.., 4, 84, 84] stacks), state the f64
+    [2 * 7056 + 1] statistics, convs three biased f32 nn.Conv2d of the script's geometry with
+    contiguous weights on the same device."""
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.uint8
+            and frames.dim() == 2 and frames.shape[0] >= 1 and frames.shape[1] == RND_BODY_FRAME
+            and frames.stride(1) == 1 and frames.data_ptr() % 4 == 0
+            and (frames.shape[0] == 1 or (frames.stride(0) >= RND_BODY_FRAME
+                                          and frames.stride(0) % 4 == 0))):
+        return False
+    if not (isinstance(state, torch.Tensor) and state.dtype == torch.float64
+            and state.device == frames.device and state.is_contiguous()
+            and state.numel() == 2 * RND_BODY_FRAME + 1):
+        return False
+    if len(convs) != 3:
+        return False
+    for m, (cin, cout, k, s) in zip(convs, _RND_BODY_GEOMETRY):
+        if not (isinstance(m, torch.nn.Conv2d) and m.in_channels == cin and m.out_channels == cout
+                and m.kernel_size == (k, k) and m.stride == (s, s) and m.padding == (0, 0)
+                and m.dilation == (1, 1) and m.groups == 1 and m.bias is not None
+                and m.weight.device == frames.device and m.weight.dtype == torch.float32
+                and m.weight.is_contiguous() and m.bias.is_contiguous()):
+            return False
+    return True
+
+
+def _rnd_body_args(who: str, frames, idx, state, convs):
+    """(device, R, the leading arguments of both entry points)."""
+    if not rnd_body_ok(frames, state, convs):
+        raise ValueError(f"{who}: needs u8 frames [rows, 7056] with 4-byte aligned rows, the f64 "
+                         f"statistics [{2 * RND_BODY_FRAME + 1}] and the script's three "
+                         f"convolutions (rnd_body_ok)")
+    dev = frames.device
+    rows = frames.shape[0]
+    R = rows if idx is None else idx.numel()
+    if R < 1:
+        raise ValueError(f"{who}: no rows")
+    ld = frames.stride(0) if rows > 1 else RND_BODY_FRAME
+    c1, c2, c3 = (m.out_channels for m in convs)
+    return dev, R, (_stream(dev), frames.data_ptr(), rows, ld,
+                    _opt(idx, "idx", torch.int64, dev), R, 84, 84, c1, c2, c3, state.data_ptr())
+
+
+def _rnd_body_params(convs):
+    return [p.data_ptr() for m in convs for p in (m.weight, m.bias)]
+
+
+def rnd_body_forward(frames, idx, state, predictor_convs, target_convs=None, save: bool = False):
+    """The body's [R, 3136] features (nn.Flatten's order) of image rows idx (None: every row) of
+    frames, normalised on chip by state: one launch, no autograd. With target_convs both
+    networks read the same on-chip frame and (predictor, target) features come back. save: also
+    the predictor's a1 [R, 12800] and a2 [R, 5184] -> (features, a1, a2)."""
+    who = "rnd_body_forward"
+    dev, R, head = _rnd_body_args(who, frames, idx, state, predictor_convs)
+    f = torch.float32
+    out = torch.empty((R, RND_BODY_FEATURES), dtype=f, device=dev)
+    tout, tparams = None, [None] * 6
+    if target_convs is not None:
+        if save or not rnd_body_ok(frames, state, target_convs):
+            raise ValueError(f"{who}: target_convs must be the script's convolutions, without save")
+        tout, tparams = torch.empty_like(out), _rnd_body_params(target_convs)
+    a1 = torch.empty((R, 32 * 400), dtype=f, device=dev) if save else None
+    a2 = torch.empty((R, 64 * 81), dtype=f, device=dev) if save else None
+    call("ocppo_rnd_body_fwd", *head, *_rnd_body_params(predictor_convs), *tparams,
+         out.data_ptr(), _opt(tout, "tout"), _opt(a1, "a1"), _opt(a2, "a2"))
+    if save:
+        return out, a1, a2
+    return out if tout is None else (out, tout)
+
+
+class _RndBody(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, frames, idx, state, convs, *params):
+        out, a1, a2 = rnd_body_forward(frames, idx, state, convs, save=True)
+        ctx.save_for_backward(out, a1, a2)
+        ctx.inputs = (frames, idx, state, convs)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        out, a1, a2 = ctx.saved_tensors
+        frames, idx, state, convs = ctx.inputs
+        dev, R, head = _rnd_body_args("rnd_body (backward)", frames, idx, state, convs)
+        f = torch.float32
+        grads = [torch.empty_like(p) for m in convs for p in (m.weight, m.bias)]
+        nb = int(_lib.LIB.ocppo_rnd_body_workspace_bytes(R))
+        ws = _persistent("rnd_body_bwd", dev, R, lambda: torch.empty(nb // 4, dtype=f, device=dev))
+        timed("rnd_body_bwd", lambda: call(
+            "ocppo_rnd_body_bwd", *head, a1.data_ptr(), a2.data_ptr(), out.data_ptr(),
+            convs[1].weight.data_ptr(), convs[2].weight.data_ptr(),
+            _check(dout.contiguous(), "dout", f, dev, R * RND_BODY_FEATURES),
+            *[g.data_ptr() for g in grads], ws.data_ptr(), ws.numel() * 4))
+        return (None, None, None, None, *grads)
+
+
+def rnd_body(frames, idx, state, convs):
+    """rnd_body_forward's predictor features under autograd: differentiable in the six parameters
+    of convs (the frames take no gradient). The backward is three launches (data-gradient chain,
+    weight-gradient chunks, ordered finish) on one workspace per R (_persistent: every call writes
+    all it reads); deterministic."""
+    params = [p for m in convs for p in (m.weight, m.bias)]
+    return _RndBody.apply(frames, idx, state, tuple(convs), *params)

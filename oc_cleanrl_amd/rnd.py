@@ -25,8 +25,8 @@ ops.rnd_mask, the package's stream, so both paths train alike from one seed).
 Declared differences from the script: no envpool / ALE here (--backend Synthetic, the package's
 device envs); `architecture` picks the networks ("RND_OBJ", the default: agents.object_trunk on
 object vectors, the RND body two Linear + LeakyReLU layers on one frame's object vector; "RND":
-the script's pixel networks -- modules, keys and init only, its trainer path is out of scope: the
-LeakyReLU convolutions have no kernel here); the observation statistics are per feature of the
+the script's pixel networks -- modules, keys and init here, trained by rnd_pixel.RNDPixelTrainer
+on the fused body kernels); the observation statistics are per feature of the
 newest frame's object vector; the update mask is the library's counter stream keyed by (seed,
 minibatch counter, row), not torch.rand; the warm-up's random actions are torch.randint from a
 device generator seeded with the run's seed, not np.random.randint, and the first rollout goes on
@@ -98,8 +98,8 @@ def finalize(args, world_size: int = 1, trainer: bool = True):
     if (args.obs_mode == "obj") != (args.architecture == "RND_OBJ"):
         raise ValueError('architecture RND_OBJ reads --obs_mode obj, RND reads pixels (dqn)')
     if trainer and args.architecture != "RND_OBJ":
-        raise NotImplementedError("RNDTrainer trains RND_OBJ; the pixel RND networks' LeakyReLU "
-                                  "convolutions have no kernel here (DESIGN 8)")
+        raise NotImplementedError("RNDTrainer trains RND_OBJ; the pixel RND networks train in "
+                                  "oc_cleanrl_amd.rnd_pixel (RNDPixelTrainer)")
     if not 0.0 <= args.update_proportion <= 1.0:
         raise ValueError(f"update_proportion {args.update_proportion} outside [0, 1]")
     if args.num_iterations_obs_norm_init < 0:
@@ -267,16 +267,19 @@ class RNDTrainer(PPOTrainer):
     two GAE scans at the rollout's end, the running observation statistics, and the intrinsic
     value + masked forward loss beside PPO's."""
 
+    ARCHITECTURE = "RND_OBJ"  # the one this class trains (rnd_pixel.RNDPixelTrainer: "RND")
+
     def __init__(self, args, device, *a, **k):
-        if args.architecture != "RND_OBJ":
-            raise NotImplementedError("RNDTrainer trains RND_OBJ only (DESIGN 8)")
+        if args.architecture != self.ARCHITECTURE:
+            raise NotImplementedError(f"{type(self).__name__} trains {self.ARCHITECTURE} only "
+                                      "(DESIGN 8)")
         self.fused = FUSED_RND
         super().__init__(args, device, *a, **k)
         if self.world != 1 or self.dp:
             raise NotImplementedError("the RND learner runs on one GPU")
         f32, dev = torch.float32, self.dev
         T, N, B, M = self.T, self.N, self.B, self.M
-        self.F = self.obs_shape[-1]
+        self.F = self._frame_features()
         D = args.rnd_feature_dim
         self.ext_values = self.values  # [T + 1, N]: PPOTrainer's value rows are the extrinsic ones
         self.int_values = torch.zeros((T + 1, N), dtype=f32, device=dev)
@@ -286,7 +289,7 @@ class RNDTrainer(PPOTrainer):
         self.ext_returns = self.returns  # what minibatch_prepare gathers beside the ext values
         self.int_returns = torch.zeros((T, N), dtype=f32, device=dev)
         self.rnd_in = torch.zeros((N, self.F), dtype=f32, device=dev)
-        self.rnd_obs = torch.zeros((B, self.F), dtype=f32, device=dev)
+        self.rnd_obs = self._batch_buffer()
         self.obs_rms = ops.rms_state(self.F, dev)
         self.reward_rms = torch.tensor([0.0, 1.0, 1e-4], dtype=torch.float64, device=dev)
         self.rewems = torch.zeros(T, dtype=f32, device=dev)
@@ -297,6 +300,14 @@ class RNDTrainer(PPOTrainer):
         self.dv_int = torch.zeros(M, dtype=f32, device=dev)
         self.rstats = torch.zeros((nmbt, len(ops.RND_STAT_NAMES)), dtype=f32, device=dev)
         self._warm_up()
+
+    def _frame_features(self) -> int:
+        """Elements of one frame: what obs_rms and the RND networks see."""
+        return self.obs_shape[-1]
+
+    def _batch_buffer(self):
+        """The batch's normalised newest frames, which the update's minibatches gather."""
+        return torch.zeros((self.B, self.F), dtype=torch.float32, device=self.dev)
 
     def _make_agent(self) -> nn.Module:
         a = self.args
@@ -447,6 +458,12 @@ class RNDTrainer(PPOTrainer):
         self._normalize(newest, self.rnd_obs)
 
     # ---- update ----------------------------------------------------------------------------
+    def _minibatch_features(self, idx):
+        """(predictor features under autograd, target features) of the batch rows idx."""
+        x = self.rnd_obs.index_select(0, idx)
+        tf = self.rnd.target_features(x)
+        return self.rnd.predict_features(x), tf
+
     def _forward_backward_body(self, j: int):
         """Minibatch j (:463-515): PPO's loss on the combined advantage and the extrinsic value
         (ops.ppo_loss_fwd_bwd), the intrinsic value loss and the masked forward loss, one
@@ -454,9 +471,7 @@ class RNDTrainer(PPOTrainer):
         a, mb = self.args, self.mb
         sl = slice(j * self.M, (j + 1) * self.M)
         logits, ve, vi = self.agent.heads3(self._minibatch_hidden(j))
-        x = self.rnd_obs.index_select(0, self.perm_dev[sl])
-        tf = self.rnd.target_features(x)
-        pf = self.rnd.predict_features(x)
+        pf, tf = self._minibatch_features(self.perm_dev[sl])
         lg, vv = logits.detach(), ve.detach().view(-1)
         self.timer.bracket("ppo_loss", lambda: ops.ppo_loss_fwd_bwd(
             lg, vv, mb["actions"][sl], mb["logprobs"][sl], mb["advantages"][sl],
