@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCPPO_ABI_VERSION 47
+#define OCPPO_ABI_VERSION 48
 
 /* status codes */
 #define OCPPO_OK 0
@@ -2022,6 +2022,55 @@ OCPPO_API int ocppo_rnd_body_bwd(ocppo_stream_t stream, const uint8_t* frames, i
                                  const float* dout, float* dw1, float* db1, float* dw2,
                                  float* db2, float* dw3, float* db3, void* workspace,
                                  size_t workspace_bytes);
+
+/* ---------------------------------------------------------------------------------------------
+ * Fused NoisyLinear layers (cleanrl/rainbow_atari_oc.py:239-279), ABI 48: for 1 or 2 layers
+ * ("groups") of the same M and K per launch,
+ *   y[M, N] = act(x[M, K] (mu + sigma * eps)^T + (bmu + bsigma * beps)),   act = ReLU when relu
+ * and its backward. f32, 1 <= M <= 128, K % 4 == 0, any N >= 1; x, mu, sigma, eps (and dmu,
+ * dsigma, dx) 16-byte aligned, everything contiguous row-major; anything else returns
+ * OCPPO_E_INVALID before any launch. w = mu + sigma * eps is one f32 multiply and one f32 add
+ * (torch's combine) and is never stored. Products on v_mfma_f32_16x16x4_f32. No float atomics:
+ * every sum has a fixed order, two runs are bitwise equal, and a group's forward bits do not depend
+ * on the other group of the launch. Graph-capturable (one launch each, no host sync).
+ *
+ * ocppo_noisy_layer_t: one layer. The forward reads x .. beps and writes y; the backward reads
+ * x, g = dL/dy [M, N], mu, sigma, eps, beps and, when relu, the forward's y (g is masked by
+ * y > 0 on load), and writes dmu [N, K] = g^T x, dsigma = dmu * eps (the f32 product of the stored
+ * dmu), dbmu [N] = sum_m g (rows in order), dbsigma = dbmu * beps and, when dx is not NULL (all
+ * groups or none), dx [M, K] = g (mu + sigma * eps). shared_x (two groups on one x, one dx):
+ * dx is the sum over both groups, group 0's part first.
+ *
+ * workspace: ocppo_noisy_linear_workspace_bytes(M, K, N0, N1 (0: one group), backward) bytes
+ * (0: sizes outside the range), 16-byte aligned, zeroed ONCE by the caller before its first use
+ * (it starts with the tickets, which every launch leaves zero); the backward needs none when dx
+ * is NULL. A shorter one returns OCPPO_E_WORKSPACE.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct ocppo_noisy_layer {
+  const float* x;
+  const float* mu;
+  const float* sigma;
+  const float* eps;
+  const float* bmu;
+  const float* bsigma;
+  const float* beps;
+  float* y;
+  const float* g;
+  float* dmu;
+  float* dsigma;
+  float* dbmu;
+  float* dbsigma;
+  float* dx;
+  int64_t N;
+} ocppo_noisy_layer_t;
+OCPPO_API size_t ocppo_noisy_linear_workspace_bytes(int64_t M, int64_t K, int64_t N0, int64_t N1,
+                                                    int backward);
+OCPPO_API int ocppo_noisy_linear_fwd(ocppo_stream_t stream, const ocppo_noisy_layer_t* layers,
+                                     int64_t groups, int64_t M, int64_t K, int relu,
+                                     void* workspace, size_t workspace_bytes);
+OCPPO_API int ocppo_noisy_linear_bwd(ocppo_stream_t stream, const ocppo_noisy_layer_t* layers,
+                                     int64_t groups, int64_t M, int64_t K, int relu, int shared_x,
+                                     void* workspace, size_t workspace_bytes);
 
 #ifdef __cplusplus
 }

@@ -5013,3 +5013,179 @@ def rnd_body(frames, idx, state, convs):
     all it reads); deterministic."""
     params = [p for m in convs for p in (m.weight, m.bias)]
     return _RndBody.apply(frames, idx, state, tuple(convs), *params)
+
+
+# ---------------------------------------------------------------------------------------------
+# Fused NoisyLinear layers (rainbow_atari_oc.py:239-279): the mu + sigma * eps combine inside the
+# Linear's operand load, forward and backward, one or two layers per launch
+# (csrc/ocppo_noisy.hip)
+# ---------------------------------------------------------------------------------------------
+# The Rainbow heads on the fused launches (off: the torch ops of NoisyLinear.forward;
+# tools/bench_rainbow.py measures both, DESIGN 12.6)
+NOISY_FUSED = True
+NOISY_MAX_ROWS = 128
+_NOISY_NAMES = ("weight_mu", "weight_sigma", "weight_epsilon", "bias_mu", "bias_sigma",
+                "bias_epsilon")
+
+
+class _NoisyLayer(ctypes.Structure):  # ocppo_noisy_layer_t
+    _fields_ = [(n, ctypes.c_void_p) for n in
+                ("x", "mu", "sigma", "eps", "bmu", "bsigma", "beps", "y", "g", "dmu", "dsigma",
+                 "dbmu", "dbsigma", "dx")] + [("N", ctypes.c_int64)]
+
+
+def _noisy_tensors(layer):
+    """(mu, sigma, eps, bmu, bsigma, beps) of a rainbow.NoisyLinear or of six tensors."""
+    if isinstance(layer, torch.nn.Module):
+        return tuple(getattr(layer, n) for n in _NOISY_NAMES)
+    return tuple(layer)
+
+
+def noisy_linear_ok(x, layers) -> bool:
+    """ops.noisy_linear applies: 1 or 2 layers (rainbow.NoisyLinear, or its six tensors) of one
+    in_features K with K % 4 == 0; x one 2-D f32 GPU tensor [M, K] shared by the layers, or one
+    per layer, 1 <= M <= 128; everything contiguous, 16-byte aligned, on one device. Anything else
+    keeps the torch ops."""
+    if not isinstance(layers, (list, tuple)) or len(layers) not in (1, 2):
+        return False
+    xs = list(x) if isinstance(x, (list, tuple)) else [x] * len(layers)
+    if len(xs) != len(layers) or not all(isinstance(t, torch.Tensor) for t in xs):
+        return False
+    x0 = xs[0]
+    if not (x0.is_cuda and x0.dim() == 2 and 1 <= x0.shape[0] <= NOISY_MAX_ROWS
+            and x0.shape[1] >= 4 and x0.shape[1] % 4 == 0):
+        return False
+    for xi, layer in zip(xs, layers):
+        ts = _noisy_tensors(layer)
+        if len(ts) != 6 or not all(isinstance(t, torch.Tensor) for t in ts):
+            return False
+        mu = ts[0]
+        if mu.dim() != 2 or mu.shape[1] != x0.shape[1] or xi.shape != x0.shape:
+            return False
+        shapes = (mu.shape,) * 3 + ((mu.shape[0],),) * 3
+        for t, shape in zip((xi, *ts), (x0.shape, *shapes)):
+            if not (t.dtype == torch.float32 and t.device == x0.device and t.shape == shape
+                    and t.is_contiguous() and t.data_ptr() % 16 == 0):
+                return False
+    return True
+
+
+def _noisy_workspace(tag: str, dev, M: int, K: int, ns, backward: bool):
+    """Tickets + partials of one shape, zeroed once (every launch leaves the tickets zero)."""
+    n1 = ns[1] if len(ns) > 1 else 0
+    nb = int(_lib.LIB.ocppo_noisy_linear_workspace_bytes(M, K, ns[0], n1, int(backward)))
+    if nb == 0:
+        raise ValueError(f"{tag}: M={M} K={K} N={tuple(ns)} is outside the kernels' range")
+    return _persistent(tag, dev, (M, K, tuple(ns)),
+                       lambda: torch.zeros(nb // 4, dtype=torch.float32, device=dev))
+
+
+class _NoisyLinear(torch.autograd.Function):
+    """tensors: the xs (one when shared, else one per layer), then six per layer."""
+
+    @staticmethod
+    def forward(ctx, relu: bool, shared: bool, need: bool, *tensors):
+        nx = 1 if shared else (len(tensors) // 7)
+        xs, params = tensors[:nx], tensors[nx:]
+        G = len(params) // 6
+        x0 = xs[0]
+        M, K = x0.shape
+        dev = x0.device
+        ys, desc = [], (_NoisyLayer * G)()
+        for i in range(G):
+            mu, sigma, eps, bmu, bsigma, beps = params[6 * i:6 * i + 6]
+            N = mu.shape[0]
+            y = torch.empty((M, N), dtype=torch.float32, device=dev)
+            ys.append(y)
+            d = desc[i]
+            d.x = xs[0 if shared else i].data_ptr()
+            d.mu, d.sigma, d.eps = mu.data_ptr(), sigma.data_ptr(), eps.data_ptr()
+            d.bmu, d.bsigma, d.beps = bmu.data_ptr(), bsigma.data_ptr(), beps.data_ptr()
+            d.y, d.N = y.data_ptr(), N
+        ws = _noisy_workspace("noisy_linear_fwd", dev, M, K, [y.shape[1] for y in ys], False)
+        timed("noisy_linear_fwd", lambda: call(
+            "ocppo_noisy_linear_fwd", _stream(dev), ctypes.addressof(desc), G, M, K, int(relu),
+            ws.data_ptr(), ws.numel() * 4))
+        if need:
+            ctx.save_for_backward(*tensors, *(ys if relu else ()))
+            ctx.geometry = (relu, shared, nx, G)
+        return tuple(ys)
+
+    @staticmethod
+    def backward(ctx, *dys):
+        relu, shared, nx, G = ctx.geometry
+        saved = ctx.saved_tensors
+        xs, params, ys = saved[:nx], saved[nx:nx + 6 * G], saved[nx + 6 * G:]
+        dxs, grads = _noisy_backward(xs, shared, params, dys, ys if relu else None,
+                                     any(ctx.needs_input_grad[3:3 + nx]))
+        return (None, None, None, *dxs, *[t for dmu, dsigma, dbmu, dbsigma in grads
+                                          for t in (dmu, dsigma, None, dbmu, dbsigma, None)])
+
+
+def _noisy_backward(xs, shared: bool, params, dys, ys, need_dx: bool):
+    """One ocppo_noisy_linear_bwd launch: ([dx per x] or [None, ...], [(dmu, dsigma, dbmu,
+    dbsigma) per layer]). ys: the forward's outputs when it applied the ReLU, else None."""
+    G, x0 = len(params) // 6, xs[0]
+    M, K = x0.shape
+    dev, f = x0.device, torch.float32
+    dxs = [torch.empty_like(x0) if need_dx else None for _ in xs]
+    grads, keep, desc = [], [], (_NoisyLayer * G)()
+    for i in range(G):
+        mu, sigma, eps, bmu, bsigma, beps = params[6 * i:6 * i + 6]
+        N = mu.shape[0]
+        g = dys[i]
+        g = torch.zeros((M, N), dtype=f, device=dev) if g is None else g.contiguous()
+        keep.append(g)  # alive until the launch is issued
+        grads.append((torch.empty_like(mu), torch.empty_like(mu), torch.empty_like(bmu),
+                      torch.empty_like(bmu)))
+        d = desc[i]
+        d.x = xs[0 if shared else i].data_ptr()
+        d.g = _check(g, "dy", f, dev, M * N)
+        d.y = None if ys is None else _check(ys[i], "y", f, dev, M * N)
+        d.mu, d.sigma, d.eps, d.beps = (mu.data_ptr(), sigma.data_ptr(), eps.data_ptr(),
+                                        beps.data_ptr())
+        d.dmu, d.dsigma, d.dbmu, d.dbsigma = (t.data_ptr() for t in grads[i])
+        d.dx = dxs[0 if shared else i].data_ptr() if need_dx else None
+        d.N = N
+    ws = _noisy_workspace("noisy_linear_bwd", dev, M, K, [p.shape[0] for p in params[::6]],
+                          True) if need_dx else None
+    timed("noisy_linear_bwd", lambda: call(
+        "ocppo_noisy_linear_bwd", _stream(dev), ctypes.addressof(desc), G, M, K,
+        int(ys is not None), int(shared and G > 1), _opt(ws, "workspace"),
+        0 if ws is None else ws.numel() * 4))
+    return dxs, grads
+
+
+def noisy_linear_backward(x, layers, dys, ys=None, need_dx: bool = True):
+    """The backward launch of noisy_linear on its own (what its autograd node runs): from
+    dys = dL/dy per layer and, when the forward applied the ReLU, its outputs ys (the mask
+    y > 0), (dx, [(dmu, dsigma, dbmu, dbsigma) per layer]) with dmu = g^T x, dsigma = dmu * eps,
+    dbmu = sum_m g, dbsigma = dbmu * beps; dx one tensor for a shared x (the sum over the
+    layers, the first layer's part first), a list for one x per layer, None without need_dx."""
+    if not noisy_linear_ok(x, layers):
+        raise ValueError("noisy_linear_backward: see noisy_linear_ok")
+    shared = not isinstance(x, (list, tuple))
+    params = [t.detach() for layer in layers for t in _noisy_tensors(layer)]
+    dxs, grads = _noisy_backward([x] if shared else list(x), shared, params, list(dys), ys,
+                                 need_dx)
+    return (dxs[0] if shared else dxs) if need_dx else None, grads
+
+
+def noisy_linear(x, layers, relu: bool = False):
+    """act(x (mu + sigma * eps)^T + (bmu + bsigma * beps)) for 1 or 2 NoisyLinear layers in one
+    launch: a tuple of [M, N_i] outputs. x: one [M, K] tensor shared by the layers (the heads'
+    first layers on the trunk output) or a list of one per layer (their second layers); layers:
+    rainbow.NoisyLinear modules or their six tensors (mu, sigma, eps, bmu, bsigma, beps). The
+    noise is always applied (a module's eval mode is the caller's branch). Differentiable in x
+    and the four parameters per layer through one backward launch that returns gradients (with a
+    shared x, dx is the sum over both layers); under torch.no_grad() nothing is saved.
+    Deterministic. Requires noisy_linear_ok(x, layers)."""
+    if not noisy_linear_ok(x, layers):
+        raise ValueError("noisy_linear: needs 1 or 2 layers of one K (K % 4 == 0) and f32 "
+                         "contiguous 16-byte aligned GPU tensors with 1 <= M <= 128 "
+                         "(noisy_linear_ok)")
+    shared = not isinstance(x, (list, tuple))
+    xs = [x] if shared else list(x)
+    params = [t for layer in layers for t in _noisy_tensors(layer)]
+    need = torch.is_grad_enabled() and any(t.requires_grad for t in (*xs, *params))
+    return _NoisyLinear.apply(bool(relu), shared, need, *xs, *params)

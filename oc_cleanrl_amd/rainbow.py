@@ -16,9 +16,10 @@ with eps = 1.5e-4 (:587) and the tau target update (:725-728). No VecNormalize.
   ops.rainbow_loss_fwd_bwd   :655-701 and its backward to the two heads' raw outputs, one launch
 everything else (env, store, FlatAdam, the fill / train chunk hipGraphs) is the DQN learner's.
 
-The trunks run on the fused Linear / convolution path (agents.fused_trunk); the noisy heads are
-torch ops (mu + sigma * eps, then the Linear), and their noise is torch's normal_() on the full
-matrices, as in the reference.
+The trunks run on the fused Linear / convolution path (agents.fused_trunk); the noisy heads run
+on ops.noisy_linear (the mu + sigma * eps combine inside the Linear's operand load, forward and
+backward, both heads per launch) where ops.noisy_linear_ok holds, else on the torch ops; their
+noise is torch's normal_() on the full matrices, as in the reference.
 """
 from __future__ import annotations
 
@@ -157,6 +158,14 @@ class NoisyDuelingDistributionalNetwork(Predictor):
         """The raw head outputs (value [len(x), N], advantage [len(x), A * N]) with the trunk on
         the fused Linear / convolution path (same math as forward up to the dueling combine)."""
         h = fused_trunk(self.network, x / 255.0)
+        v1, v2 = self.value_head[0], self.value_head[2]
+        a1, a2 = self.advantage_head[0], self.advantage_head[2]
+        if ops.NOISY_FUSED and self.training and ops.noisy_linear_ok(h, (v1, a1)):
+            # two launches: both first layers (+ ReLU) on the shared h, then both second layers
+            hv, ha = ops.noisy_linear(h, (v1, a1), relu=True)
+            if ops.noisy_linear_ok((hv, ha), (v2, a2)):
+                return ops.noisy_linear((hv, ha), (v2, a2))
+            return v2(hv), a2(ha)
         return self.value_head(h), self.advantage_head(h)
 
     def forward(self, x):
@@ -256,7 +265,7 @@ class RainbowTrainer(DQNTrainer):
                                  dvalue=self.dvalue, dadvantage=self.dadvantage,
                                  loss_per_sample=self.loss_per_sample, stats=self.td_stats)
         self.rb.update_priorities(d["indices"], self.loss_per_sample)  # :704-705
-        self.opt.zero_grad()  # the heads' gradients accumulate (torch ops)
+        self.opt.zero_grad()  # the heads' gradients accumulate (autograd)
         torch.autograd.backward([value, advantage], [self.dvalue, self.dadvantage])
         self.opt.step()
 

@@ -10,9 +10,12 @@
   3. env steps per second of RainbowTrainer, C51Trainer and DQNTrainer (config 5) at the config-5
      sizes (SpaceInvaders obj-mode, 1 env, 1M-transition replay, batch 32, train_frequency 4) in
      the training phase.
+  4. (--noisy) the fused NoisyLinear launches (ops.noisy_linear, forward and backward) against
+     the torch ops they replace, per launch in a replayed graph, and RainbowTrainer's env steps
+     per second with ops.NOISY_FUSED on and off, object and pixel observations.
 Every case runs twice, alternating; both runs are reported.
 
-    python tools/bench_rainbow.py [--steps K] [--warmup W] [--skip-trainer]
+    python tools/bench_rainbow.py [--steps K] [--warmup W] [--skip-trainer] [--noisy]
 """
 import argparse
 import json
@@ -201,6 +204,61 @@ def bench_replay(dev, capacity=1_000_000, B=32, obs_shape=(4, 12), fill=5000):
     return res
 
 
+def bench_noisy(dev, n=20):
+    """Per launch as a replayed hipGraph of n launches: ops.noisy_linear on both first layers
+    (K -> 512 twice, shared x, ReLU) and both second layers (512 -> 51 and 306) at M = 1 and 32,
+    and ops.noisy_linear_backward at M = 32, each against the torch ops it replaces
+    (NoisyLinear.forward, autograd); object (K = 32) and pixel (K = 3136) trunks. Bytes are the
+    kernels' global traffic counted from the code: mu, sigma, eps once per direction, x, y / g,
+    the K-split partials (forward) and dmu, dsigma and the partial dx (backward)."""
+    from oc_cleanrl_amd.rainbow import NoisyLinear
+
+    lib, res = ops._lib.LIB, {}
+    relu = torch.nn.functional.relu
+    for trunk, K1 in (("object", 32), ("pixel", 3136)):
+        for name, K, ns, shared in (("layer1", K1, (512, 512), True), ("layer2", 512, (51, 306), False)):
+            layers = [NoisyLinear(K, N).to(dev) for N in ns]
+            nk = sum(ns) * K
+            for M in (1, 32):
+                xs = [torch.randn(M, K, device=dev, requires_grad=True) for _ in range(1 if shared else 2)]
+                x = xs[0] if shared else xs
+                gs = [torch.randn(M, N, device=dev) for N in ns]
+                act = (lambda t: relu(t)) if shared else (lambda t: t)
+                torch_fwd = lambda: [act(l(xs[0 if shared else i])) for i, l in enumerate(layers)]  # noqa: E731
+                params = [p for l in layers for p in l.parameters()]
+
+                def fused_fwd():
+                    with torch.no_grad():
+                        return ops.noisy_linear(x, layers, relu=shared)
+
+                def torch_pair():
+                    return torch.autograd.grad(torch_fwd(), xs + params, gs)
+
+                ys = [y.detach() for y in fused_fwd()]
+                for _ in range(3):  # the BLAS library sets itself up outside the capture
+                    torch_pair()
+                torch.cuda.synchronize()
+                fused_bwd = lambda: ops.noisy_linear_backward(x, layers, gs, ys if shared else None)  # noqa: E731
+                with torch.no_grad():
+                    gt = graph_of(torch_fwd, n)
+                cases = {"fused_fwd": graph_of(fused_fwd, n), "torch_fwd": gt}
+                part = lib.ocppo_noisy_linear_workspace_bytes(M, K, ns[0], ns[1], 0) - 16384
+                bytes_ = {"fused_fwd": 12 * nk + 4 * M * (len(xs) * K + sum(ns)) + 2 * part}
+                if M == 32:
+                    torch_pair(), fused_bwd()
+                    cases.update(fused_bwd=graph_of(fused_bwd, n), torch_fwd_bwd=graph_of(torch_pair, n))
+                    part = lib.ocppo_noisy_linear_workspace_bytes(M, K, ns[0], ns[1], 1) - 16384
+                    bytes_["fused_bwd"] = 20 * nk + 4 * M * (2 * len(xs) * K + 2 * sum(ns)) + 2 * part
+                us = {k: [] for k in cases}
+                for _ in range(2):  # alternating
+                    for k, g in cases.items():
+                        us[k].append(round(timed(g.replay, 30) / n, 2))
+                res[f"{trunk}_{name}_M{M}"] = {
+                    "us_per_launch": us, "bytes": bytes_,
+                    "TB_per_s": {k: [round(b / t * 1e-6, 3) for t in us[k]] for k, b in bytes_.items()}}
+    return res
+
+
 def bench_trainer(cls, args, dev, steps, warmup):
     tr = cls(args, dev, log=False)
     tr.steps(args.learning_starts + warmup)
@@ -216,8 +274,24 @@ def main():
     ap.add_argument("--steps", type=int, default=20000)
     ap.add_argument("--warmup", type=int, default=2000)
     ap.add_argument("--skip-trainer", action="store_true")
+    ap.add_argument("--noisy", action="store_true", help="only the fused NoisyLinear cases")
     o = ap.parse_args()
     dev = torch.device("cuda:0")
+    if o.noisy:  # the noisy-head launches and the trainer with the heads fused / on the torch ops
+        out = {"noisy_linear": bench_noisy(dev), "rainbow_env_steps_per_sec": {}}
+        for obs_mode in () if o.skip_trainer else ("obj", "dqn"):
+            kw = dict(env_id="ALE/SpaceInvaders-v5", obs_mode=obs_mode, num_envs=1,
+                      buffer_size=1_000_000 if obs_mode == "obj" else 50_000, learning_starts=1000,
+                      total_timesteps=10_000_000, save_model=False)
+            sps = out["rainbow_env_steps_per_sec"][obs_mode] = {"fused": [], "torch_ops": []}
+            for _ in range(2):  # alternating
+                for name, flag in (("fused", True), ("torch_ops", False)):
+                    ops.NOISY_FUSED = flag
+                    sps[name].append(bench_trainer(RainbowTrainer, RainbowArgs(**kw), dev, o.steps,
+                                                   o.warmup))
+            ops.NOISY_FUSED = True
+        print(json.dumps(out))
+        return
     out = {"loss_kernel": bench_loss(dev), "replay": bench_replay(dev)}
     if not o.skip_trainer:
         kw = dict(env_id="ALE/SpaceInvaders-v5", obs_mode="obj", num_envs=1, buffer_size=1_000_000,
