@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCPPO_ABI_VERSION 48
+#define OCPPO_ABI_VERSION 49
 
 /* status codes */
 #define OCPPO_OK 0
@@ -2070,6 +2070,60 @@ OCPPO_API int ocppo_noisy_linear_fwd(ocppo_stream_t stream, const ocppo_noisy_la
                                      void* workspace, size_t workspace_bytes);
 OCPPO_API int ocppo_noisy_linear_bwd(ocppo_stream_t stream, const ocppo_noisy_layer_t* layers,
                                      int64_t groups, int64_t M, int64_t K, int relu, int shared_x,
+                                     void* workspace, size_t workspace_bytes);
+
+/* ---------------------------------------------------------------------------------------------
+ * The pixel ViT (cleanrl/ppo_atari_vit.py: vit_pytorch's SimpleViT behind nn.Flatten), ABI 49. The
+ * two pieces of it that are neither a Linear nor a LayerNorm over a short row. All f32,
+ * deterministic (no atomics: two runs are bitwise equal), graph-capturable.
+ *
+ * ocppo_vit_attn_fwd: unmasked multi-head attention on v_mfma_f32_16x16x4_f32 (exact f32
+ * products, f32 accumulation), one 256-thread workgroup per (sample, head).
+ *   qkv : [B, S, 3 I] (q | k | v), I = heads * dh, each (h d): to_qkv(x).chunk(3, -1), and the
+ *         layout of ocppo_mha_fwd
+ *   out : [B, S, I]   out_i = sum_j softmax_j(dh^-0.5 q_i . k_j) v_j over all S keys
+ *   lse : [B, heads, S] log-sum-exp of each query's scaled scores
+ * Contract: 1 <= S <= 64, dh = I / heads in {32, 64}, I <= 512, B >= 1, B * heads < 2^31, qkv and
+ * out 16-byte aligned; anything else returns OCPPO_E_INVALID before any launch.
+ *
+ * ocppo_vit_attn_bwd: its backward. P is recomputed from qkv and lse, D_i = dout_i . out_i,
+ * dS = P (dP - D). Writes EVERY element of dqkv [B, S, 3 I].
+ *
+ * ocppo_vit_patch_ln_fwd: Rearrange('b c (h p1) (w p2) -> b (h w) (p1 p2 c)') + LayerNorm(C p^2)
+ * read from u8 frame stacks.
+ *   src   : [rows, C, H, H] u8, 4-byte aligned
+ *   idx   : [R] int64 rows of src (an index outside [0, rows) is clamped into it, never
+ *           dereferenced), or NULL: rows 0 .. R - 1
+ *   y     : [R * T, C p^2] f32, T = (H / p)^2, token t = (h, w), column (p1 p + p2) C + c
+ *           y = LayerNorm(x) * gamma + beta on the raw 0-255 values (no division by 255)
+ *   mean, rstd : [R * T], written
+ * The first mean is float(exact integer sum) / E, correctly rounded; the row is then re-centred
+ * once and the variance is the mean of the squared deviations (ocppo_ln_relu_fwd's scheme);
+ * rstd = 1 / sqrt(var + eps). A constant patch gives y = beta exactly. R = 0 launches nothing.
+ * Contract: H = 84, p in {12, 14, 21}, 1 <= C <= 8, rows >= 1.
+ *
+ * ocppo_vit_patch_ln_bwd: dgamma, dbeta [C p^2] from dy [R * T, C p^2], with x^ = (x - mean) rstd
+ * recomputed from src (pixels get no gradient). min(R * H / p, 256) workgroups -- a function of
+ * R and p alone -- each store one partial [2][C p^2] to the workspace
+ * (ocppo_vit_patch_workspace_bytes(R, C, p); 0 outside the contract; a shorter or NULL buffer
+ * returns OCPPO_E_WORKSPACE) with plain stores; a second launch of the same call adds the partials
+ * in workgroup order. R >= 1.
+ * ------------------------------------------------------------------------------------------- */
+OCPPO_API int ocppo_vit_attn_fwd(ocppo_stream_t stream, const float* qkv, int64_t B, int64_t S,
+                                 int64_t I, int64_t heads, float* out, float* lse);
+OCPPO_API int ocppo_vit_attn_bwd(ocppo_stream_t stream, const float* qkv, const float* out,
+                                 const float* lse, const float* dout, int64_t B, int64_t S,
+                                 int64_t I, int64_t heads, float* dqkv);
+OCPPO_API int ocppo_vit_patch_ln_fwd(ocppo_stream_t stream, const uint8_t* src,
+                                     const int64_t* idx, int64_t rows, int64_t R, int64_t C,
+                                     int64_t H, int64_t patch, const float* gamma,
+                                     const float* beta, double eps, float* y, float* mean,
+                                     float* rstd);
+OCPPO_API size_t ocppo_vit_patch_workspace_bytes(int64_t R, int64_t C, int64_t patch);
+OCPPO_API int ocppo_vit_patch_ln_bwd(ocppo_stream_t stream, const float* dy, const uint8_t* src,
+                                     const int64_t* idx, int64_t rows, int64_t R, int64_t C,
+                                     int64_t H, int64_t patch, const float* mean,
+                                     const float* rstd, float* dgamma, float* dbeta,
                                      void* workspace, size_t workspace_bytes);
 
 #ifdef __cplusplus

@@ -2954,6 +2954,158 @@ def mha(qkv, key_valid, heads: int, rng=None, site: int = 0, p: float = 0.0):
     return _MHADropout.apply(qkv, key_valid, heads, rng, site, float(p))
 
 
+# ---------------------------------------------------------------------------------------------
+# the pixel ViT (ppo_atari_vit.py: vit_pytorch's SimpleViT): unmasked attention on the f32 MFMA
+# (csrc/ocppo_vit_attn.hip) and patchify + LayerNorm from the u8 stacks (csrc/ocppo_vit_patch.hip)
+# ---------------------------------------------------------------------------------------------
+VIT_ATTN_MAX_S, VIT_ATTN_MAX_I, VIT_ATTN_HEAD_DIMS = 64, 512, (32, 64)
+VIT_PATCH_H, VIT_PATCH_SIZES, VIT_PATCH_MAX_C = 84, (12, 14, 21), 8
+
+
+def vit_attn_shape_ok(S: int, I: int, heads: int) -> bool:
+    """The contract of ocppo_vit_attn_fwd / _bwd (I = heads * dh, the inner width)."""
+    return (1 <= S <= VIT_ATTN_MAX_S and 1 <= I <= VIT_ATTN_MAX_I and heads >= 1 and
+            I % heads == 0 and I // heads in VIT_ATTN_HEAD_DIMS)
+
+
+def _vit_attn_shape(qkv, heads: int, who: str):
+    if qkv.dim() != 3 or qkv.shape[2] % 3:
+        raise ValueError(f"{who}: qkv must be [B, S, 3I], got {tuple(qkv.shape)}")
+    B, S, I3 = qkv.shape
+    if B < 1 or not vit_attn_shape_ok(S, I3 // 3, heads):
+        raise ValueError(f"{who}: unsupported B={B} S={S} I={I3 // 3} heads={heads} "
+                         "(vit_attn_shape_ok)")
+    return B, S, I3 // 3
+
+
+def vit_attn_fwd(qkv, heads: int, out=None, lse=None):
+    """softmax(dh^-0.5 q k^T) v per head, no mask: qkv [B, S, 3I] f32 (q | k | v, each (h d)) ->
+    (out [B, S, I], lse [B, heads, S])."""
+    B, S, I = _vit_attn_shape(qkv, heads, "vit_attn_fwd")
+    dev, f = qkv.device, torch.float32
+    out = torch.empty((B, S, I), dtype=f, device=dev) if out is None else out
+    lse = torch.empty((B, heads, S), dtype=f, device=dev) if lse is None else lse
+    call("ocppo_vit_attn_fwd", _stream(dev), _check(qkv, "qkv", f, dev), B, S, I, heads,
+         _check(out, "out", f, dev, B * S * I), _check(lse, "lse", f, dev, B * heads * S))
+    return out, lse
+
+
+def vit_attn_bwd(qkv, out, lse, dout, heads: int, dqkv=None):
+    """d qkv [B, S, 3I] of vit_attn_fwd (every element written)."""
+    B, S, I = _vit_attn_shape(qkv, heads, "vit_attn_bwd")
+    dev, f = qkv.device, torch.float32
+    dqkv = torch.empty_like(qkv) if dqkv is None else dqkv
+    call("ocppo_vit_attn_bwd", _stream(dev), _check(qkv, "qkv", f, dev),
+         _check(out, "out", f, dev, B * S * I), _check(lse, "lse", f, dev, B * heads * S),
+         _check(dout, "dout", f, dev, B * S * I), B, S, I, heads,
+         _check(dqkv, "dqkv", f, dev, B * S * 3 * I))
+    return dqkv
+
+
+# vit_attn at B * heads problems below this runs ops.mha's rows-in-lanes kernel instead (same
+# math, key_valid None). 0: the MFMA kernel everywhere, which is what the measurements of
+# DESIGN.md 27 call for.
+VIT_ATTN_MFMA_MIN_PROBLEMS = 0
+
+
+class _ViTAttn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, heads: int):
+        qkv = qkv.detach().contiguous()
+        out, lse = vit_attn_fwd(qkv, heads)
+        ctx.save_for_backward(qkv, out, lse)
+        ctx.heads = heads
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        qkv, out, lse = ctx.saved_tensors
+        return vit_attn_bwd(qkv, out, lse, g.contiguous(), ctx.heads), None
+
+
+def vit_attn(qkv, heads: int):
+    """Differentiable vit_attn_fwd: [B, S, 3I] -> [B, S, I] (the heads concatenated, for to_out)."""
+    if qkv.shape[0] * heads < VIT_ATTN_MFMA_MIN_PROBLEMS:
+        return _MHA.apply(qkv, None, heads)
+    return _ViTAttn.apply(qkv, heads)
+
+
+def vit_patch_ok(src, ln, patch: int) -> bool:
+    """vit_patch_ln applies: contiguous GPU u8 stacks [N, C, 84, 84] with 1 <= C <= 8, patch in
+    {12, 14, 21} and an affine nn.LayerNorm over C * patch^2."""
+    return (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.uint8 and
+            src.dim() == 4 and src.is_contiguous() and src.shape[0] >= 1 and
+            1 <= src.shape[1] <= VIT_PATCH_MAX_C and
+            tuple(src.shape[2:]) == (VIT_PATCH_H, VIT_PATCH_H) and patch in VIT_PATCH_SIZES and
+            isinstance(ln, torch.nn.LayerNorm) and ln.elementwise_affine and
+            ln.bias is not None and
+            tuple(ln.normalized_shape) == (src.shape[1] * patch * patch,))
+
+
+def _vit_patch_shape(src, idx, patch: int, who: str):
+    if src.dim() != 4 or src.shape[0] < 1 or not 1 <= src.shape[1] <= VIT_PATCH_MAX_C or \
+            tuple(src.shape[2:]) != (VIT_PATCH_H, VIT_PATCH_H) or patch not in VIT_PATCH_SIZES:
+        raise ValueError(f"{who}: src {tuple(src.shape)} patch {patch}: [N, C <= "
+                         f"{VIT_PATCH_MAX_C}, 84, 84] u8 stacks, patch in {VIT_PATCH_SIZES}")
+    N, C = src.shape[:2]
+    R = N if idx is None else idx.numel()
+    return N, C, R, (VIT_PATCH_H // patch) ** 2, C * patch * patch
+
+
+def vit_patch_ln_fwd(src, idx, weight, bias, patch: int, eps: float = 1e-5):
+    """LayerNorm over the (p1 p2 c) patches of u8 stacks src [N, C, 84, 84], rows idx [R] i64 (None:
+    every row in order), on the raw 0-255 values -> (y [R, T, C p^2], mean [R T], rstd [R T])."""
+    N, C, R, T, E = _vit_patch_shape(src, idx, patch, "vit_patch_ln_fwd")
+    dev, f = src.device, torch.float32
+    y = torch.empty((R, T, E), dtype=f, device=dev)
+    mean = torch.empty(R * T, dtype=f, device=dev)
+    rstd = torch.empty(R * T, dtype=f, device=dev)
+    call("ocppo_vit_patch_ln_fwd", _stream(dev), _check(src, "src", torch.uint8, dev),
+         _opt(idx, "idx", torch.int64, dev), N, R, C, VIT_PATCH_H, patch,
+         _check(weight, "weight", f, dev, E), _check(bias, "bias", f, dev, E), float(eps),
+         y.data_ptr(), mean.data_ptr(), rstd.data_ptr())
+    return y, mean, rstd
+
+
+def vit_patch_ln_bwd(dy, src, idx, mean, rstd, patch: int):
+    """(dweight, dbias) [C p^2] of vit_patch_ln_fwd. The partials live in one buffer per size
+    (_persistent): every call writes all the partials it reads."""
+    N, C, R, T, E = _vit_patch_shape(src, idx, patch, "vit_patch_ln_bwd")
+    dev, f = src.device, torch.float32
+    dw = torch.empty(E, dtype=f, device=dev)
+    db = torch.empty(E, dtype=f, device=dev)
+    nb = int(_lib.LIB.ocppo_vit_patch_workspace_bytes(R, C, patch))
+    ws = _persistent("vit_patch_ln_bwd", dev, nb, lambda: torch.empty(
+        max(nb // 4, 1), dtype=f, device=dev))
+    call("ocppo_vit_patch_ln_bwd", _stream(dev), _check(dy, "dy", f, dev, R * T * E),
+         _check(src, "src", torch.uint8, dev), _opt(idx, "idx", torch.int64, dev), N, R, C,
+         VIT_PATCH_H, patch, _check(mean, "mean", f, dev, R * T), _check(rstd, "rstd", f, dev, R * T),
+         dw.data_ptr(), db.data_ptr(), ws.data_ptr(), nb)
+    return dw, db
+
+
+class _ViTPatchLn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, src, idx, weight, bias, patch: int, eps: float):
+        y, mean, rstd = vit_patch_ln_fwd(src, idx, weight.detach(), bias.detach(), patch, eps)
+        ctx.save_for_backward(src, idx, mean, rstd)
+        ctx.patch = patch
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        src, idx, mean, rstd = ctx.saved_tensors
+        dw, db = timed("vit_patch_ln_bwd", lambda: vit_patch_ln_bwd(g.contiguous(), src, idx, mean,
+                                                                    rstd, ctx.patch))
+        return None, None, dw, db, None, None
+
+
+def vit_patch_ln(src, idx, ln, patch: int):
+    """Differentiable (in ln's weight and bias) patchify + LayerNorm of SimpleViT's
+    to_patch_embedding[0:2] from the u8 stacks: [N, C, 84, 84], idx [R] or None -> [R, T, C p^2]."""
+    return _ViTPatchLn.apply(src, idx, ln.weight, ln.bias, patch, ln.eps)
+
+
 # The two LayerNorms (add_layernorm_* here, ln_relu_* with the PQN kernels below) are one kernel
 # skeleton (csrc/ocppo_layernorm.h) behind two pairs of entries; so are their wrappers.
 def _ln_shape(x, res, weight, bias, max_e: int, who: str):
