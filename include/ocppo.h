@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCPPO_ABI_VERSION 49
+#define OCPPO_ABI_VERSION 50
 
 /* status codes */
 #define OCPPO_OK 0
@@ -2125,6 +2125,45 @@ OCPPO_API int ocppo_vit_patch_ln_bwd(ocppo_stream_t stream, const float* dy, con
                                      int64_t H, int64_t patch, const float* mean,
                                      const float* rstd, float* dgamma, float* dbeta,
                                      void* workspace, size_t workspace_bytes);
+
+/* ---------------------------------------------------------------------------------------------
+ * The feed-forward half of a SimpleViT block as one launch (csrc/ocppo_vit_ffn.hip), ABI 50:
+ *   y = x + W2 gelu(W1 u + b1) + b2,  u = LayerNorm(x) * gamma + beta
+ * on v_mfma_f32_16x16x4_f32 (f32 operands and accumulation), exact GELU
+ * 0.5 z (1 + erf(z / sqrt 2)). Deterministic (no atomics: two runs are bitwise equal),
+ * graph-capturable, no scratch.
+ *   x, y, dy, dx : [rows, D]    W1 : [H, D], b1 : [H]    W2 : [D, H], b2 : [D]    gamma, beta : [D]
+ * Contract: rows >= 1, D and H multiples of 32 in [32, 128] (they may differ), W1 and W2 16-byte
+ * aligned; anything else, or a null required pointer, returns OCPPO_E_INVALID before any launch
+ * and touches no output. rows == 0 launches nothing and returns OCPPO_OK.
+ *
+ * ocppo_vit_ffn_fwd: 256-thread workgroups over 64-row tiles, both weight slices of a wave in
+ * registers. The LayerNorm statistics follow ocppo_ln_relu_fwd (mean, re-centre once, variance =
+ * mean of the squared deviations, rstd = 1 / sqrt(var + eps)); a constant row gives u == beta
+ * bitwise. mean, rstd [rows] are written when both are non-NULL; both NULL (the no-grad call)
+ * writes neither.
+ *
+ * ocppo_vit_ffn_bwd: dx = dy + LN'(du), dgamma, dbeta, dW1, db1, dW2, db2 from dy, x, the saved
+ * mean / rstd and the parameters; u, z = W1 u + b1 and h = gelu(z) are recomputed per tile. EVERY
+ * element of the seven outputs is written (no accumulation into them). min(ceil(rows / 64), 128)
+ * 512-thread workgroups -- a function of rows alone -- keep dW1 / dW2 in MFMA accumulators over
+ * their tiles and store one partial each to the workspace (ocppo_vit_ffn_workspace_bytes(rows, D,
+ * H); 0 outside the contract; 16-byte aligned, no initial contents needed; a shorter or NULL
+ * buffer returns OCPPO_E_WORKSPACE) with plain stores; a second launch of the same call adds the
+ * partials in workgroup order in f64. The column sums db1, db2, dgamma, dbeta are a balanced tree
+ * over the rows of a tile in f32, then f64 over tiles, waves and workgroups.
+ * ------------------------------------------------------------------------------------------- */
+OCPPO_API int ocppo_vit_ffn_fwd(ocppo_stream_t stream, const float* x, const float* gamma,
+                                const float* beta, const float* W1, const float* b1,
+                                const float* W2, const float* b2, int64_t rows, int64_t D,
+                                int64_t H, double eps, float* y, float* mean, float* rstd);
+OCPPO_API size_t ocppo_vit_ffn_workspace_bytes(int64_t rows, int64_t D, int64_t H);
+OCPPO_API int ocppo_vit_ffn_bwd(ocppo_stream_t stream, const float* dy, const float* x,
+                                const float* mean, const float* rstd, const float* gamma,
+                                const float* beta, const float* W1, const float* b1,
+                                const float* W2, int64_t rows, int64_t D, int64_t H, float* dx,
+                                float* dgamma, float* dbeta, float* dW1, float* db1, float* dW2,
+                                float* db2, void* workspace, size_t workspace_bytes);
 
 #ifdef __cplusplus
 }

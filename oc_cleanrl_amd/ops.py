@@ -3106,6 +3106,122 @@ def vit_patch_ln(src, idx, ln, patch: int):
     return _ViTPatchLn.apply(src, idx, ln.weight, ln.bias, patch, ln.eps)
 
 
+# The feed-forward half of a ViT block, y = x + W2 gelu(W1 LN(x) + b1) + b2, as one launch forward
+# and one (+ finish) backward (csrc/ocppo_vit_ffn.hip, f32 MFMA)
+VIT_FFN_MIN_DIM, VIT_FFN_MAX_DIM, VIT_FFN_DIM_STEP = 32, 128, 32
+VIT_FFN_TILE_ROWS, VIT_FFN_MAX_PARTS = 64, 128  # rows per tile; workgroups (partials) of the backward
+# Callers with another route (vit.ViTAgent.trunk_stacks: the chain of launches) take vit_ffn
+# between these row counts: the learner's captured rollout step (490 rows: 8
+# workgroups) is faster on the chain, and so is a 65,536-row call (the backward stops at 128
+# workgroups); 15,680 rows (the default minibatch) is measured faster fused. The crossovers
+# inside (490, 15,680) and (15,680, 65,536) were not located.
+VIT_FFN_MIN_ROWS, VIT_FFN_MAX_ROWS = 1024, 16384
+
+
+def vit_ffn_routed(rows: int) -> bool:
+    return VIT_FFN_MIN_ROWS <= rows <= VIT_FFN_MAX_ROWS
+
+
+def _vit_ffn_dim_ok(v: int) -> bool:
+    return VIT_FFN_MIN_DIM <= v <= VIT_FFN_MAX_DIM and v % VIT_FFN_DIM_STEP == 0
+
+
+def vit_ffn_ok(x, ff) -> bool:
+    """vit_ffn applies to rows x [rows, D] and the FeedForward module ff (net = LayerNorm, Linear,
+    GELU, Linear): affine LayerNorm with bias, both Linears with bias, the exact GELU, D and H in
+    the contract, contiguous f32 GPU tensors."""
+    net = getattr(ff, "net", None)
+    if net is None or len(net) != 4:
+        return False
+    ln, l1, act, l2 = net
+    if not (isinstance(ln, torch.nn.LayerNorm) and isinstance(l1, torch.nn.Linear) and
+            isinstance(act, torch.nn.GELU) and isinstance(l2, torch.nn.Linear)):
+        return False
+    if not ln.elementwise_affine or ln.bias is None or l1.bias is None or l2.bias is None or \
+            act.approximate != "none":
+        return False
+    D, H = l1.in_features, l1.out_features
+    ts = (x, ln.weight, ln.bias, l1.weight, l1.bias, l2.weight, l2.bias)
+    return (isinstance(x, torch.Tensor) and x.dim() == 2 and x.shape[0] >= 1 and x.shape[1] == D and
+            tuple(ln.normalized_shape) == (D,) and (l2.in_features, l2.out_features) == (H, D) and
+            _vit_ffn_dim_ok(D) and _vit_ffn_dim_ok(H) and
+            all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in ts))
+
+
+def _vit_ffn_shape(x, W1, who: str):
+    if x.dim() != 2 or W1.dim() != 2 or x.shape[0] < 1 or x.shape[1] != W1.shape[1] or \
+            not _vit_ffn_dim_ok(W1.shape[1]) or not _vit_ffn_dim_ok(W1.shape[0]):
+        raise ValueError(f"{who}: x {tuple(x.shape)}, W1 {tuple(W1.shape)}: rows >= 1, D and H "
+                         f"multiples of {VIT_FFN_DIM_STEP} in [{VIT_FFN_MIN_DIM}, {VIT_FFN_MAX_DIM}]")
+    return x.shape[0], W1.shape[1], W1.shape[0]
+
+
+def vit_ffn_fwd(x, gamma, beta, W1, b1, W2, b2, eps: float = 1e-5, stats: bool = True, y=None,
+                mean=None, rstd=None):
+    """x + W2 gelu(W1 LN(x) + b1) + b2 on rows x [rows, D] -> (y, mean [rows], rstd [rows]); stats
+    False (the no-grad call): the statistics are not written and come back None."""
+    R, D, H = _vit_ffn_shape(x, W1, "vit_ffn_fwd")
+    dev, f = x.device, torch.float32
+    y = torch.empty_like(x) if y is None else y
+    if stats:
+        mean = torch.empty(R, dtype=f, device=dev) if mean is None else mean
+        rstd = torch.empty(R, dtype=f, device=dev) if rstd is None else rstd
+    else:
+        mean = rstd = None
+    call("ocppo_vit_ffn_fwd", _stream(dev), _check(x, "x", f, dev), _check(gamma, "gamma", f, dev, D),
+         _check(beta, "beta", f, dev, D), _check(W1, "W1", f, dev, H * D), _check(b1, "b1", f, dev, H),
+         _check(W2, "W2", f, dev, D * H), _check(b2, "b2", f, dev, D), R, D, H, float(eps),
+         _check(y, "y", f, dev, R * D), _opt(mean, "mean", f, dev, R), _opt(rstd, "rstd", f, dev, R))
+    return y, mean, rstd
+
+
+def vit_ffn_bwd(dy, x, mean, rstd, gamma, beta, W1, b1, W2, out=None):
+    """(dx, dgamma, dbeta, dW1, db1, dW2, db2) of vit_ffn_fwd, every element written. The partials
+    live in one buffer per size (_persistent): every call writes all the partials it reads."""
+    R, D, H = _vit_ffn_shape(x, W1, "vit_ffn_bwd")
+    dev, f = x.device, torch.float32
+    if out is None:
+        out = (torch.empty_like(x), torch.empty_like(gamma), torch.empty_like(beta),
+               torch.empty_like(W1), torch.empty_like(b1), torch.empty_like(W2),
+               torch.empty(D, dtype=f, device=dev))
+    nb = int(_lib.LIB.ocppo_vit_ffn_workspace_bytes(R, D, H))
+    ws = _persistent("vit_ffn_bwd", dev, nb, lambda: torch.empty(nb // 8, dtype=torch.float64,
+                                                                 device=dev))
+    call("ocppo_vit_ffn_bwd", _stream(dev), _check(dy, "dy", f, dev, R * D), _check(x, "x", f, dev),
+         _check(mean, "mean", f, dev, R), _check(rstd, "rstd", f, dev, R),
+         _check(gamma, "gamma", f, dev, D), _check(beta, "beta", f, dev, D),
+         _check(W1, "W1", f, dev, H * D), _check(b1, "b1", f, dev, H), _check(W2, "W2", f, dev, D * H),
+         R, D, H, *(_check(t, "out", f, dev, n) for t, n in zip(out, (R * D, D, D, H * D, H, D * H, D))),
+         ws.data_ptr(), nb)
+    return out
+
+
+class _ViTFFN(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, W1, b1, W2, b2, eps: float):
+        x = x.detach().contiguous()
+        p = tuple(t.detach() for t in (gamma, beta, W1, b1, W2))
+        y, mean, rstd = vit_ffn_fwd(x, *p, b2.detach(), eps)
+        ctx.save_for_backward(x, mean, rstd, *p)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, mean, rstd, *p = ctx.saved_tensors
+        return (*timed("vit_ffn_bwd", lambda: vit_ffn_bwd(g.contiguous(), x, mean, rstd, *p)), None)
+
+
+def vit_ffn(x, ff):
+    """Differentiable x + ff(x) for rows x [rows, D] and a FeedForward module (vit_ffn_ok must
+    hold). Without a graph to build (torch.no_grad(), the rollout) the forward writes no
+    statistics."""
+    ln, l1, _, l2 = ff.net
+    p = (ln.weight, ln.bias, l1.weight, l1.bias, l2.weight, l2.bias)
+    if not torch.is_grad_enabled() or not (x.requires_grad or any(t.requires_grad for t in p)):
+        return vit_ffn_fwd(x.detach().contiguous(), *(t.detach() for t in p), ln.eps, stats=False)[0]
+    return _ViTFFN.apply(x, *p, ln.eps)
+
+
 # The two LayerNorms (add_layernorm_* here, ln_relu_* with the PQN kernels below) are one kernel
 # skeleton (csrc/ocppo_layernorm.h) behind two pairs of entries; so are their wrappers.
 def _ln_shape(x, res, weight, bias, max_e: int, who: str):

@@ -14,8 +14,10 @@ The fused path (`FUSED_VIT`, `ViTAgent.fused_ok`) reads the rollout's u8 stacks 
 indices: ops.vit_patch_ln (patchify + the first LayerNorm, csrc/ocppo_vit_patch.hip), the Linears
 on agents.linear_act, the pre-norm LayerNorms on ops.ln_relu(relu=False) (the last LayerNorm on
 torch's: FINAL_NORM_HIP), the attention core on
-ops.vit_attn (csrc/ocppo_vit_attn.hip, f32 MFMA); GELU, the residual adds, the positional add and
-the token mean are torch ops. The two bias-free Linears of a block (to_qkv, to_out) run
+ops.vit_attn (csrc/ocppo_vit_attn.hip, f32 MFMA), the feed-forward half of a block (LayerNorm,
+Linear, exact GELU, Linear, residual add) on ops.vit_ffn (`FUSED_FFN`, csrc/ocppo_vit_ffn.hip, f32
+MFMA; outside ops.vit_ffn_ok: ops.ln_relu, linear_act and torch's GELU and add); the attention
+half's residual add, the positional add and the token mean are torch ops. The two bias-free Linears of a block (to_qkv, to_out) run
 ops.linear_act in the rollout and F.linear under autograd: agents._LinearAct's update GEMM routes
 take a bias. Shapes outside either kernel contract (e.g. patch_size 6) and `FUSED_VIT = False` run
 the same modules in plain torch.
@@ -47,6 +49,12 @@ FUSED_VIT = True
 # the project's error rule. The two pre-norms of every block and the patch embedding's norm, whose
 # gradient rows differ, stay on ops.ln_relu.
 FINAL_NORM_HIP = False
+
+# The feed-forward half of every block (pre-norm LayerNorm, Linear, GELU, Linear and the residual
+# add) as ops.vit_ffn: one launch forward, two backward (csrc/ocppo_vit_ffn.hip). A FeedForward
+# outside ops.vit_ffn_ok (e.g. mlp_dim 256), a row count outside ops.vit_ffn_routed (the 490-row
+# rollout step: measured slower fused) and False run the chain of launches below it.
+FUSED_FFN = True
 
 DIM_HEAD = 64  # vit_pytorch's default, which the script does not override
 
@@ -252,6 +260,9 @@ class ViTAgent(_ActorCritic):
             qkv = _linear_nobias(_norm(x, attn.norm), attn.to_qkv)
             a = ops.vit_attn(qkv.view(R, T, qkv.shape[1]), heads)
             x = _linear_nobias(a.view(R * T, -1), attn.to_out) + x
+            if FUSED_FFN and ops.vit_ffn_routed(x.shape[0]) and ops.vit_ffn_ok(x, ff):
+                x = ops.vit_ffn(x, ff)
+                continue
             h = F.gelu(linear_act(_norm(x, ff.net[0]), ff.net[1], False))
             x = linear_act(h, ff.net[3], False) + x
         x = _norm(x, v.transformer.norm) if FINAL_NORM_HIP else v.transformer.norm(x)
