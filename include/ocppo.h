@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCPPO_ABI_VERSION 50
+#define OCPPO_ABI_VERSION 51
 
 /* status codes */
 #define OCPPO_OK 0
@@ -2164,6 +2164,54 @@ OCPPO_API int ocppo_vit_ffn_bwd(ocppo_stream_t stream, const float* dy, const fl
                                 const float* W2, int64_t rows, int64_t D, int64_t H, float* dx,
                                 float* dgamma, float* dbeta, float* dW1, float* db1, float* dW2,
                                 float* db2, void* workspace, size_t workspace_bytes);
+
+/* ---------------------------------------------------------------------------------------------
+ * The attention half of a SimpleViT block as one launch (csrc/ocppo_vit_attn_block.hip), ABI 51:
+ *   u = LayerNorm(x) * gamma + beta,  qkv = u Wqkv^T,  O_h = softmax(q_h k_h^T / 8) v_h per
+ *   (sample, head),  y = x + concat_h(O_h) Wout^T
+ * on v_mfma_f32_16x16x4_f32 (f32 operands and accumulation), no biases. qkv, the attention output
+ * and their gradients stay on the chip. Deterministic (no atomics: two runs are bitwise equal),
+ * graph-capturable, no scratch.
+ *   x, y, dy, dx : [B * S, D], sample-major, S tokens per sample    gamma, beta : [D]
+ *   Wqkv : [3 I, D], rows q | k | v, each head-major (I = 64 heads)    Wout : [D, I]
+ *   mean, rstd : [B * S]    lse : [B, heads, S]
+ * Contract: B >= 1, 1 <= S <= 64, D a multiple of 32 in [32, 128], head width 64, 1 <= heads <= 8,
+ * Wqkv and Wout 16-byte aligned; anything else, or a null required pointer, returns
+ * OCPPO_E_INVALID before any launch and touches no output. B == 0 launches nothing and returns
+ * OCPPO_OK.
+ *
+ * ocppo_vit_attn_block_fwd: one 256-thread workgroup per sample (grid-stride beyond 2048). The
+ * LayerNorm statistics follow ocppo_ln_relu_fwd (mean, re-centre once, variance = mean of the
+ * squared deviations, rstd = 1 / sqrt(var + eps)); a constant row gives u == beta bitwise. Padded
+ * key columns S .. 63 are -inf before the row maximum. mean, rstd and lse are written when all
+ * three are non-NULL; all NULL (the no-grad call) writes none of them and gives the same y.
+ *
+ * ocppo_vit_attn_block_bwd: dx = dy + LN'(du), dgamma, dbeta, dWqkv, dWout from dy, x, the saved
+ * mean / rstd / lse and the parameters; u, q, k, v, P and O are recomputed per (sample, head).
+ * EVERY element of the five outputs is written (no accumulation into them). heads * P 512-thread
+ * workgroups, P = min(B, 256 / heads) -- a function of B and heads alone -- each own one head, walk
+ * samples p, p + P, ... with the head's weight gradients in MFMA accumulators, store one partial
+ * and write du_h to the head's slab of the workspace (ocppo_vit_attn_block_workspace_bytes(B, S, D,
+ * heads): the slabs [heads, B * S, D], the partials and the column partials; 0 outside the
+ * contract; 16-byte aligned, no initial contents needed; a shorter or NULL buffer returns
+ * OCPPO_E_WORKSPACE with nothing launched) with plain stores. Two further launches of the same
+ * call add the slabs in head order and run the LayerNorm backward and the residual, then add the
+ * weight partials in workgroup order in f64. dgamma and dbeta are a balanced tree over 16 rows in
+ * f32, then f64 over tiles, workgroups and waves.
+ * ------------------------------------------------------------------------------------------- */
+OCPPO_API int ocppo_vit_attn_block_fwd(ocppo_stream_t stream, const float* x, const float* gamma,
+                                       const float* beta, const float* Wqkv, const float* Wout,
+                                       int64_t B, int64_t S, int64_t D, int64_t heads, double eps,
+                                       float* y, float* mean, float* rstd, float* lse);
+OCPPO_API size_t ocppo_vit_attn_block_workspace_bytes(int64_t B, int64_t S, int64_t D,
+                                                      int64_t heads);
+OCPPO_API int ocppo_vit_attn_block_bwd(ocppo_stream_t stream, const float* dy, const float* x,
+                                       const float* mean, const float* rstd, const float* lse,
+                                       const float* gamma, const float* beta, const float* Wqkv,
+                                       const float* Wout, int64_t B, int64_t S, int64_t D,
+                                       int64_t heads, float* dx, float* dgamma, float* dbeta,
+                                       float* dWqkv, float* dWout, void* workspace,
+                                       size_t workspace_bytes);
 
 #ifdef __cplusplus
 }

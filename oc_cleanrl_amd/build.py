@@ -47,13 +47,15 @@ HIP_FLAGS = [
 # ocppo_noisy.hip: the same guard; its VALU work is the mu + sigma * eps combine and the
 # dsigma = dmu * eps product on a stream bound by memory traffic.
 # ocppo_vit_ffn.hip: the same guard; LayerNorm, GELU and bias epilogues beside MFMAs.
+# ocppo_vit_attn_block.hip: the same guard; LayerNorm and softmax epilogues beside MFMAs.
 NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 FILE_FLAGS = {"ocppo_gemm.hip": ["-fno-slp-vectorize"],
               "ocppo_impala.hip": NO_PACKED_F32,
               "ocppo_ln_chw.hip": NO_PACKED_F32,
               "ocppo_rnd_body.hip": NO_PACKED_F32,
               "ocppo_noisy.hip": NO_PACKED_F32,
-              "ocppo_vit_ffn.hip": NO_PACKED_F32}
+              "ocppo_vit_ffn.hip": NO_PACKED_F32,
+              "ocppo_vit_attn_block.hip": NO_PACKED_F32}
 
 
 def sources() -> list[Path]:

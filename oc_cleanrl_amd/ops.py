@@ -3222,6 +3222,139 @@ def vit_ffn(x, ff):
     return _ViTFFN.apply(x, *p, ln.eps)
 
 
+# The attention half of a ViT block, y = x + to_out(attention(to_qkv(LN(x)))), as one launch forward
+# and one (+ two finish) backward (csrc/ocppo_vit_attn_block.hip, f32 MFMA)
+VIT_ATTN_BLOCK_MIN_DIM, VIT_ATTN_BLOCK_MAX_DIM, VIT_ATTN_BLOCK_DIM_STEP = 32, 128, 32
+VIT_ATTN_BLOCK_MAX_S, VIT_ATTN_BLOCK_DIM_HEAD, VIT_ATTN_BLOCK_MAX_HEADS = 64, 64, 8
+VIT_ATTN_BLOCK_PART_TARGET = 256  # the backward runs about this many head-owning workgroups
+
+
+def vit_attn_block_parts(B: int, heads: int) -> int:
+    """Workgroups per head of the backward (the partials the finish adds): min(B, cap), the cap a
+    function of heads alone."""
+    return max(1, min(B, VIT_ATTN_BLOCK_PART_TARGET // heads))
+
+
+# Callers with another route (vit.ViTAgent.trunk_stacks: the chain of launches) take vit_attn_block
+# between these sample counts. The range is EMPTY: measured (DESIGN.md 27.5), the learner is slower
+# with the fused half at the rollout's 10 samples (8,781 against 13,961 env steps / s), at the
+# 320-sample minibatch (10,796) and at both (7,395), so the default is the chain everywhere.
+VIT_ATTN_BLOCK_MIN_SAMPLES, VIT_ATTN_BLOCK_MAX_SAMPLES = 1, 0
+
+
+def vit_attn_block_routed(B: int) -> bool:
+    return VIT_ATTN_BLOCK_MIN_SAMPLES <= B <= VIT_ATTN_BLOCK_MAX_SAMPLES
+
+
+def _vit_attn_block_sizes_ok(S: int, D: int, heads: int) -> bool:
+    return (1 <= S <= VIT_ATTN_BLOCK_MAX_S and 1 <= heads <= VIT_ATTN_BLOCK_MAX_HEADS and
+            VIT_ATTN_BLOCK_MIN_DIM <= D <= VIT_ATTN_BLOCK_MAX_DIM and
+            D % VIT_ATTN_BLOCK_DIM_STEP == 0)
+
+
+def vit_attn_block_ok(x, attn, S: int) -> bool:
+    """vit_attn_block applies to rows x [B * S, D] (sample-major) and the vit.Attention module attn
+    (norm = affine LayerNorm with bias, to_qkv and to_out bias-free Linears, heads of width 64):
+    shapes in the contract, contiguous f32 GPU tensors."""
+    ln, qkv, out = (getattr(attn, n, None) for n in ("norm", "to_qkv", "to_out"))
+    heads = getattr(attn, "heads", None)
+    if not (isinstance(ln, torch.nn.LayerNorm) and isinstance(qkv, torch.nn.Linear) and
+            isinstance(out, torch.nn.Linear) and isinstance(heads, int)):
+        return False
+    if not ln.elementwise_affine or ln.bias is None or qkv.bias is not None or out.bias is not None:
+        return False
+    D, I = qkv.in_features, VIT_ATTN_BLOCK_DIM_HEAD * heads
+    ts = (x, ln.weight, ln.bias, qkv.weight, out.weight)
+    return (isinstance(x, torch.Tensor) and x.dim() == 2 and x.shape[0] >= 1 and x.shape[1] == D and
+            S >= 1 and x.shape[0] % S == 0 and tuple(ln.normalized_shape) == (D,) and
+            qkv.out_features == 3 * I and (out.in_features, out.out_features) == (I, D) and
+            _vit_attn_block_sizes_ok(S, D, heads) and
+            all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in ts))
+
+
+def _vit_attn_block_shape(x, Wqkv, S: int, who: str):
+    ok = x.dim() == 2 and Wqkv.dim() == 2 and x.shape[0] >= 1 and x.shape[1] == Wqkv.shape[1] and \
+        S >= 1 and x.shape[0] % S == 0 and Wqkv.shape[0] % (3 * VIT_ATTN_BLOCK_DIM_HEAD) == 0
+    heads = Wqkv.shape[0] // (3 * VIT_ATTN_BLOCK_DIM_HEAD) if ok else 0
+    if not ok or not _vit_attn_block_sizes_ok(S, x.shape[1], heads):
+        raise ValueError(f"{who}: x {tuple(x.shape)}, Wqkv {tuple(Wqkv.shape)}, S {S}: rows a "
+                         f"multiple of S <= {VIT_ATTN_BLOCK_MAX_S}, D a multiple of "
+                         f"{VIT_ATTN_BLOCK_DIM_STEP} in [{VIT_ATTN_BLOCK_MIN_DIM}, "
+                         f"{VIT_ATTN_BLOCK_MAX_DIM}], 1 to {VIT_ATTN_BLOCK_MAX_HEADS} heads of 64")
+    return x.shape[0] // S, x.shape[1], heads
+
+
+def vit_attn_block_fwd(x, gamma, beta, Wqkv, Wout, S: int, eps: float = 1e-5, stats: bool = True,
+                       y=None, mean=None, rstd=None, lse=None):
+    """x + concat_h(softmax(q_h k_h^T / 8) v_h) Wout^T with q | k | v = LN(x) Wqkv^T on rows x
+    [B * S, D] -> (y, mean [B S], rstd [B S], lse [B, heads, S]); stats False (the no-grad call):
+    the three saved arrays are not written and come back None."""
+    B, D, heads = _vit_attn_block_shape(x, Wqkv, S, "vit_attn_block_fwd")
+    dev, f, I = x.device, torch.float32, VIT_ATTN_BLOCK_DIM_HEAD * heads
+    y = torch.empty_like(x) if y is None else y
+    if stats:
+        mean = torch.empty(B * S, dtype=f, device=dev) if mean is None else mean
+        rstd = torch.empty(B * S, dtype=f, device=dev) if rstd is None else rstd
+        lse = torch.empty(B, heads, S, dtype=f, device=dev) if lse is None else lse
+    else:
+        mean = rstd = lse = None
+    call("ocppo_vit_attn_block_fwd", _stream(dev), _check(x, "x", f, dev),
+         _check(gamma, "gamma", f, dev, D), _check(beta, "beta", f, dev, D),
+         _check(Wqkv, "Wqkv", f, dev, 3 * I * D), _check(Wout, "Wout", f, dev, D * I), B, S, D, heads,
+         float(eps), _check(y, "y", f, dev, B * S * D), _opt(mean, "mean", f, dev, B * S),
+         _opt(rstd, "rstd", f, dev, B * S), _opt(lse, "lse", f, dev, B * heads * S))
+    return y, mean, rstd, lse
+
+
+def vit_attn_block_bwd(dy, x, mean, rstd, lse, gamma, beta, Wqkv, Wout, S: int, out=None):
+    """(dx, dgamma, dbeta, dWqkv, dWout) of vit_attn_block_fwd, every element written. The du slabs
+    and the partials live in one buffer per size (_persistent): every call writes all it reads."""
+    B, D, heads = _vit_attn_block_shape(x, Wqkv, S, "vit_attn_block_bwd")
+    dev, f, I = x.device, torch.float32, VIT_ATTN_BLOCK_DIM_HEAD * heads
+    if out is None:
+        out = (torch.empty_like(x), torch.empty_like(gamma), torch.empty_like(beta),
+               torch.empty_like(Wqkv), torch.empty_like(Wout))
+    nb = int(_lib.LIB.ocppo_vit_attn_block_workspace_bytes(B, S, D, heads))
+    ws = _persistent("vit_attn_block_bwd", dev, nb, lambda: torch.empty(
+        nb // 8, dtype=torch.float64, device=dev))
+    call("ocppo_vit_attn_block_bwd", _stream(dev), _check(dy, "dy", f, dev, B * S * D),
+         _check(x, "x", f, dev), _check(mean, "mean", f, dev, B * S),
+         _check(rstd, "rstd", f, dev, B * S), _check(lse, "lse", f, dev, B * heads * S),
+         _check(gamma, "gamma", f, dev, D), _check(beta, "beta", f, dev, D),
+         _check(Wqkv, "Wqkv", f, dev, 3 * I * D), _check(Wout, "Wout", f, dev, D * I), B, S, D, heads,
+         *(_check(t, "out", f, dev, n) for t, n in zip(out, (B * S * D, D, D, 3 * I * D, D * I))),
+         ws.data_ptr(), nb)
+    return out
+
+
+class _ViTAttnBlock(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, Wqkv, Wout, S: int, eps: float):
+        x = x.detach().contiguous()
+        p = tuple(t.detach() for t in (gamma, beta, Wqkv, Wout))
+        y, mean, rstd, lse = vit_attn_block_fwd(x, *p, S, eps)
+        ctx.save_for_backward(x, mean, rstd, lse, *p)
+        ctx.S = S
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, mean, rstd, lse, *p = ctx.saved_tensors
+        return (*timed("vit_attn_block_bwd", lambda: vit_attn_block_bwd(
+            g.contiguous(), x, mean, rstd, lse, *p, ctx.S)), None, None)
+
+
+def vit_attn_block(x, attn, S: int):
+    """Differentiable x + attn(x) for rows x [B * S, D] and a vit.Attention module
+    (vit_attn_block_ok must hold). Without a graph to build (torch.no_grad(), the rollout) the
+    forward writes no statistics."""
+    p = (attn.norm.weight, attn.norm.bias, attn.to_qkv.weight, attn.to_out.weight)
+    if not torch.is_grad_enabled() or not (x.requires_grad or any(t.requires_grad for t in p)):
+        return vit_attn_block_fwd(x.detach().contiguous(), *(t.detach() for t in p), S,
+                                  attn.norm.eps, stats=False)[0]
+    return _ViTAttnBlock.apply(x, *p, S, attn.norm.eps)
+
+
 # The two LayerNorms (add_layernorm_* here, ln_relu_* with the PQN kernels below) are one kernel
 # skeleton (csrc/ocppo_layernorm.h) behind two pairs of entries; so are their wrappers.
 def _ln_shape(x, res, weight, bias, max_e: int, who: str):

@@ -17,9 +17,13 @@ torch's: FINAL_NORM_HIP), the attention core on
 ops.vit_attn (csrc/ocppo_vit_attn.hip, f32 MFMA), the feed-forward half of a block (LayerNorm,
 Linear, exact GELU, Linear, residual add) on ops.vit_ffn (`FUSED_FFN`, csrc/ocppo_vit_ffn.hip, f32
 MFMA; outside ops.vit_ffn_ok: ops.ln_relu, linear_act and torch's GELU and add); the attention
-half's residual add, the positional add and the token mean are torch ops. The two bias-free Linears of a block (to_qkv, to_out) run
-ops.linear_act in the rollout and F.linear under autograd: agents._LinearAct's update GEMM routes
-take a bias. Shapes outside either kernel contract (e.g. patch_size 6) and `FUSED_VIT = False` run
+half of a block (LayerNorm, to_qkv, the attention core, to_out, residual add) on ops.vit_attn_block
+(`FUSED_ATTN`, csrc/ocppo_vit_attn_block.hip, f32 MFMA) at the sample counts ops.vit_attn_block_routed
+names; the positional add and the token mean are torch ops. Outside that routing (the default: the
+routed range is empty) or ops.vit_attn_block_ok the attention half is a chain:
+ops.ln_relu, to_qkv, ops.vit_attn, to_out and torch's add, where the two bias-free Linears run
+ops.linear_act in the rollout and F.linear under autograd (agents._LinearAct's update GEMM routes
+take a bias). Shapes outside either kernel contract (e.g. patch_size 6) and `FUSED_VIT = False` run
 the same modules in plain torch.
 
 Declared differences from the script: `--backend Synthetic` (no ALE here) and `obs_mode dqn`, this
@@ -55,6 +59,12 @@ FINAL_NORM_HIP = False
 # outside ops.vit_ffn_ok (e.g. mlp_dim 256), a row count outside ops.vit_ffn_routed (the 490-row
 # rollout step: measured slower fused) and False run the chain of launches below it.
 FUSED_FFN = True
+
+# The attention half of every block (pre-norm LayerNorm, to_qkv, softmax attention, to_out and the
+# residual add) as ops.vit_attn_block: one launch forward, three backward
+# (csrc/ocppo_vit_attn_block.hip). An Attention outside ops.vit_attn_block_ok, a sample count
+# outside ops.vit_attn_block_routed and False run the chain of launches below it.
+FUSED_ATTN = True
 
 DIM_HEAD = 64  # vit_pytorch's default, which the script does not override
 
@@ -257,9 +267,12 @@ class ViTAgent(_ActorCritic):
         D = x.shape[1]
         x = (x.view(R, T, D) + v.pos_embedding).view(R * T, D)
         for attn, ff in v.transformer.layers:
-            qkv = _linear_nobias(_norm(x, attn.norm), attn.to_qkv)
-            a = ops.vit_attn(qkv.view(R, T, qkv.shape[1]), heads)
-            x = _linear_nobias(a.view(R * T, -1), attn.to_out) + x
+            if FUSED_ATTN and ops.vit_attn_block_routed(R) and ops.vit_attn_block_ok(x, attn, T):
+                x = ops.vit_attn_block(x, attn, T)
+            else:
+                qkv = _linear_nobias(_norm(x, attn.norm), attn.to_qkv)
+                a = ops.vit_attn(qkv.view(R, T, qkv.shape[1]), heads)
+                x = _linear_nobias(a.view(R * T, -1), attn.to_out) + x
             if FUSED_FFN and ops.vit_ffn_routed(x.shape[0]) and ops.vit_ffn_ok(x, ff):
                 x = ops.vit_ffn(x, ff)
                 continue
