@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCPPO_ABI_VERSION 51
+#define OCPPO_ABI_VERSION 52
 
 /* status codes */
 #define OCPPO_OK 0
@@ -2212,6 +2212,46 @@ OCPPO_API int ocppo_vit_attn_block_bwd(ocppo_stream_t stream, const float* dy, c
                                        int64_t heads, float* dx, float* dgamma, float* dbeta,
                                        float* dWqkv, float* dWout, void* workspace,
                                        size_t workspace_bytes);
+
+/* ---------------------------------------------------------------------------------------------
+ * The object-set transformer agent's trunk, inference forward, as one launch
+ * (csrc/ocppo_oct_trunk.hip), ABI 52: object sets x [B, S, F] -> the pooled hidden [B, E],
+ *   valid[s] = any(x[b, s, :num_obj] != 0) (masking);  h = x W_enc^T + b_enc;
+ *   per block (torch's post-norm TransformerEncoderLayer, dim_feedforward == E, ReLU, no dropout):
+ *     h = LN1(h + out_proj(attention(in_proj(h))));  h = LN2(h + linear2(relu(linear1(h))));
+ *   masking: `post` Linear + ReLU layers (skipped with masking off, as the reference does);
+ *   pooling OCPPO_OCT_POOL_MAX (masking: rows times the mask first), _MEAN (masking: the sum of ALL
+ *   rows over the valid count) or _FIRST (row 0).
+ * All Linears on v_mfma_f32_16x16x4_f32 (f32 operands and accumulation), attention per head as
+ * softmax(q k^T / sqrt(dh)) v with excluded keys weighted exactly 0, LayerNorm with the biased
+ * variance about the mean. A workgroup carries whole samples from the input to the pooled output;
+ * activations stay in LDS. Deterministic (no atomics), graph-capturable, no workspace, no
+ * backward. A sample without a valid key gives NaN in its own row of hidden and no fault.
+ *   params : HOST array of 2 + 12 * blocks + 2 * post device pointers, read during the call (they
+ *            travel in the kernel argument): encoder weight [E, F], bias [E]; per block in_proj
+ *            weight [3E, E], bias [3E], out_proj weight [E, E], bias [E], norm1 weight, bias [E],
+ *            linear1 weight [E, E], bias [E], linear2 weight [E, E], bias [E], norm2 weight, bias
+ *            [E]; per post layer weight [E, E], bias [E]. Weights row-major [out, in] as torch holds
+ *            them; every [., E] weight 16-byte aligned (the encoder's [E, F] needs 4 bytes only)
+ *   eps    : HOST array of 2 * blocks doubles (norm1, norm2 per block); may be NULL at blocks == 0
+ *   tile_rows : token rows per workgroup, 16 / 32 / 64 and >= S, or 0 for
+ *            ocppo_oct_trunk_tile_rows(B, S) (the smallest tile holding a whole sample that leaves
+ *            at most 256 workgroups, else 64; 0 outside 1 <= B, 1 <= S <= 64)
+ * Contract: B >= 1, 1 <= S <= 64, 1 <= F <= 64, E a multiple of 16 in [16, 128], heads | E with
+ * head dim in {8, 16, 32, 64}, 0 <= blocks <= 8, 0 <= post <= 4, 1 <= num_obj <= F; anything else,
+ * or a null pointer, returns OCPPO_E_INVALID before any launch and touches no output.
+ * ------------------------------------------------------------------------------------------- */
+#define OCPPO_OCT_POOL_MAX 0
+#define OCPPO_OCT_POOL_MEAN 1
+#define OCPPO_OCT_POOL_FIRST 2
+#define OCPPO_OCT_MAX_BLOCKS 8
+#define OCPPO_OCT_MAX_POST 4
+OCPPO_API int ocppo_oct_trunk_fwd(ocppo_stream_t stream, const float* x,
+                                  const float* const* params, const double* eps, int64_t B,
+                                  int64_t S, int64_t F, int64_t E, int64_t heads, int64_t blocks,
+                                  int64_t post, int64_t num_obj, int masking, int pooling,
+                                  int64_t tile_rows, float* hidden);
+OCPPO_API int64_t ocppo_oct_trunk_tile_rows(int64_t B, int64_t S);
 
 #ifdef __cplusplus
 }

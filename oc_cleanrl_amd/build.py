@@ -48,6 +48,7 @@ HIP_FLAGS = [
 # dsigma = dmu * eps product on a stream bound by memory traffic.
 # ocppo_vit_ffn.hip: the same guard; LayerNorm, GELU and bias epilogues beside MFMAs.
 # ocppo_vit_attn_block.hip: the same guard; LayerNorm and softmax epilogues beside MFMAs.
+# ocppo_oct_trunk.hip: the same guard; bias, residual and LayerNorm epilogues beside MFMAs.
 NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 FILE_FLAGS = {"ocppo_gemm.hip": ["-fno-slp-vectorize"],
               "ocppo_impala.hip": NO_PACKED_F32,
@@ -55,7 +56,8 @@ FILE_FLAGS = {"ocppo_gemm.hip": ["-fno-slp-vectorize"],
               "ocppo_rnd_body.hip": NO_PACKED_F32,
               "ocppo_noisy.hip": NO_PACKED_F32,
               "ocppo_vit_ffn.hip": NO_PACKED_F32,
-              "ocppo_vit_attn_block.hip": NO_PACKED_F32}
+              "ocppo_vit_attn_block.hip": NO_PACKED_F32,
+              "ocppo_oct_trunk.hip": NO_PACKED_F32}
 
 
 def sources() -> list[Path]:

@@ -28,6 +28,7 @@
 // The p = 0 instantiations carry none of this and are the kernels as they were.
 #include <math.h>
 
+#include "ocppo_attn_rows.h"
 #include "ocppo_common.h"
 #include "ocppo_layernorm.h"
 #include "ocppo_philox.h"
@@ -38,51 +39,6 @@ constexpr int kAttnMaxS = 64;
 // residual add + LayerNorm: ocppo_layernorm.h's kernels at E <= 512, 8 columns per lane for every E
 constexpr int kLnMaxE = 512;
 constexpr int kLnPerLane = kLnMaxE / kWave;
-
-// sum_d a[d] * row[d]: four interleaved FMA chains, combined (0 + 1) + (2 + 3). Every score and
-// every dP of this file goes through here with the register operand first.
-template <int DH>
-__device__ __forceinline__ float dot_row(const float (&a)[DH], const float* __restrict__ row) {
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-#pragma unroll
-  for (int c = 0; c < DH / 4; ++c) {
-    const float4 r = *reinterpret_cast<const float4*>(row + 4 * c);
-    s0 = fmaf(a[4 * c + 0], r.x, s0);
-    s1 = fmaf(a[4 * c + 1], r.y, s1);
-    s2 = fmaf(a[4 * c + 2], r.z, s2);
-    s3 = fmaf(a[4 * c + 3], r.w, s3);
-  }
-  return (s0 + s1) + (s2 + s3);
-}
-
-template <int DH>
-__device__ __forceinline__ void axpy_row(float (&acc)[DH], float a, const float* __restrict__ row) {
-#pragma unroll
-  for (int c = 0; c < DH / 4; ++c) {
-    const float4 r = *reinterpret_cast<const float4*>(row + 4 * c);
-    acc[4 * c + 0] = fmaf(a, r.x, acc[4 * c + 0]);
-    acc[4 * c + 1] = fmaf(a, r.y, acc[4 * c + 1]);
-    acc[4 * c + 2] = fmaf(a, r.z, acc[4 * c + 2]);
-    acc[4 * c + 3] = fmaf(a, r.w, acc[4 * c + 3]);
-  }
-}
-
-template <int DH>
-__device__ __forceinline__ void load_row(float (&v)[DH], const float* __restrict__ src) {
-#pragma unroll
-  for (int c = 0; c < DH / 4; ++c) {
-    const float4 r = *reinterpret_cast<const float4*>(src + 4 * c);
-    v[4 * c + 0] = r.x; v[4 * c + 1] = r.y; v[4 * c + 2] = r.z; v[4 * c + 3] = r.w;
-  }
-}
-
-template <int DH>
-__device__ __forceinline__ void store_row(float* __restrict__ dst, const float (&v)[DH], float mul) {
-#pragma unroll
-  for (int c = 0; c < DH / 4; ++c)
-    *reinterpret_cast<float4*>(dst + 4 * c) = make_float4(
-        v[4 * c + 0] * mul, v[4 * c + 1] * mul, v[4 * c + 2] * mul, v[4 * c + 3] * mul);
-}
 
 // S rows of DH floats at `src` (row stride `stride` floats) -> an LDS tile of row stride DH + 4
 template <int DH>

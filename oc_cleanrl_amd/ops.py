@@ -3106,6 +3106,108 @@ def vit_patch_ln(src, idx, ln, patch: int):
     return _ViTPatchLn.apply(src, idx, ln.weight, ln.bias, patch, ln.eps)
 
 
+# The object-set transformer agent's whole trunk, inference forward, as one launch
+# (csrc/ocppo_oct_trunk.hip, f32 MFMA): object sets [B, S, F] -> pooled hidden [B, E]
+OCT_MAX_S, OCT_MAX_F, OCT_MIN_E, OCT_MAX_E, OCT_E_STEP = 64, 64, 16, 128, 16
+OCT_POOLING = {"max": _lib.OCPPO_OCT_POOL_MAX, "mean": _lib.OCPPO_OCT_POOL_MEAN,
+               "first": _lib.OCPPO_OCT_POOL_FIRST}
+# Callers with another route (transformer.OCTransformerAgent.trunk: the chain of launches) take
+# oct_trunk at S <= 16 objects and between these token-row counts B * S: the measured range (S 8
+# and 16; 80 rows = the script's 10 envs x 8 objects, 65,536 = 4096 x 16), inside which the kernel
+# beat the chain at every measured size in both runs, trunk alone and trainer.
+# Outside it the chain stays. S decides the tile: 17 .. 32 objects need 32-row workgroups and
+# 33 .. 64 need 64-row ones; the trunk alone at S 32 and 64 lost to the chain at 3 and 10 envs
+# (171 against 143 us, 277 against 207 us) and won from 128 envs, the crossover was not located
+# and no trainer run was taken there. Below 80 rows nothing was measured; two existing tests at
+# 30 and 48 rows compare such paths bitwise or at a tight data-dependent bound.
+OCT_TRUNK_MAX_S = 16
+OCT_TRUNK_MIN_ROWS, OCT_TRUNK_MAX_ROWS = 80, 65536
+
+
+def oct_trunk_routed(B: int, S: int) -> bool:
+    return S <= OCT_TRUNK_MAX_S and OCT_TRUNK_MIN_ROWS <= B * S <= OCT_TRUNK_MAX_ROWS
+
+
+def _oct_params(encoder, layers, post_layers):
+    """The parameter tensors in the order of ocppo_oct_trunk_fwd's host array."""
+    ps = [encoder.weight, encoder.bias]
+    for ly in layers:
+        sa = ly.self_attn
+        ps += [sa.in_proj_weight, sa.in_proj_bias, sa.out_proj.weight, sa.out_proj.bias,
+               ly.norm1.weight, ly.norm1.bias, ly.linear1.weight, ly.linear1.bias,
+               ly.linear2.weight, ly.linear2.bias, ly.norm2.weight, ly.norm2.bias]
+    for lin in post_layers:
+        ps += [lin.weight, lin.bias]
+    return ps
+
+
+def oct_trunk_ok(x, encoder, layers, post_layers, num_heads: int, num_obj: int,
+                 pooling_type: str) -> bool:
+    """oct_trunk applies: x [B, S, F] GPU f32 contiguous inside the size contract, `layers`
+    torch TransformerEncoderLayers in the agent's form (post-norm, ReLU, dim_feedforward == E,
+    affine LayerNorms, biases everywhere), `post_layers` Linear(E, E) with bias, every parameter
+    a contiguous f32 tensor on x's device with 16-byte aligned [E]-wide weights."""
+    if not (isinstance(x, torch.Tensor) and x.dim() == 3 and x.is_cuda and
+            x.dtype == torch.float32 and x.is_contiguous()):
+        return False
+    B, S, F = x.shape
+    E = encoder.out_features
+    if not (B >= 1 and 1 <= S <= OCT_MAX_S and 1 <= F <= OCT_MAX_F and encoder.in_features == F and
+            OCT_MIN_E <= E <= OCT_MAX_E and E % OCT_E_STEP == 0 and num_heads >= 1 and
+            E % num_heads == 0 and E // num_heads in MHA_HEAD_DIMS and
+            len(layers) <= _lib.OCPPO_OCT_MAX_BLOCKS and len(post_layers) <= _lib.OCPPO_OCT_MAX_POST
+            and 1 <= num_obj <= F and pooling_type in OCT_POOLING and encoder.bias is not None):
+        return False
+    for ly in layers:
+        sa = ly.self_attn
+        if not (isinstance(ly, torch.nn.TransformerEncoderLayer) and not ly.norm_first and
+                ly.activation is torch.nn.functional.relu and sa.num_heads == num_heads and
+                sa.embed_dim == E and sa._qkv_same_embed_dim and sa.in_proj_bias is not None and
+                sa.bias_k is None and not sa.add_zero_attn and sa.out_proj.bias is not None and
+                (ly.linear1.in_features, ly.linear1.out_features) == (E, E) and
+                (ly.linear2.in_features, ly.linear2.out_features) == (E, E) and
+                ly.linear1.bias is not None and ly.linear2.bias is not None and
+                all(n.elementwise_affine and n.bias is not None and
+                    tuple(n.normalized_shape) == (E,) for n in (ly.norm1, ly.norm2))):
+            return False
+    if not all(isinstance(lin, torch.nn.Linear) and lin.bias is not None and
+               (lin.in_features, lin.out_features) == (E, E) for lin in post_layers):
+        return False
+    ps = _oct_params(encoder, layers, post_layers)
+    return all(t.device == x.device and t.dtype == torch.float32 and t.is_contiguous()
+               for t in ps) and all(t.data_ptr() % 16 == 0 for t in ps[2:] if t.dim() == 2)
+
+
+def oct_trunk_tile_rows(B: int, S: int) -> int:
+    """Token rows per workgroup that ocppo_oct_trunk_fwd picks for (B, S)."""
+    return int(_lib.LIB.ocppo_oct_trunk_tile_rows(B, S))
+
+
+def oct_trunk(x, encoder, layers, post_layers, num_heads: int, masking: bool, num_obj: int,
+              pooling_type: str, tile_rows: int = 0, out=None, checked: bool = False):
+    """The pooled hidden [B, E] of the object sets x [B, S, F] (OCTransformerAgent.trunk at dropout
+    0, no autograd graph): encoder Linear, every block, the post layers (masking only, as the
+    reference) and the pooling in one launch on the current stream. oct_trunk_ok is the contract
+    (`checked`: the caller has just evaluated it on these arguments, so its walk over every
+    parameter is not repeated; the C entry still checks sizes, pointers and alignment);
+    tile_rows 16 / 32 / 64 overrides the kernel's tile rule (tools)."""
+    if not checked and not oct_trunk_ok(x, encoder, layers, post_layers, num_heads, num_obj,
+                                        pooling_type):
+        raise ValueError("oct_trunk: outside the contract (oct_trunk_ok)")
+    B, S, F = x.shape
+    E = encoder.out_features
+    dev, f = x.device, torch.float32
+    ps = _oct_params(encoder, layers, post_layers)
+    ptrs = (ctypes.c_void_p * len(ps))(*(t.data_ptr() for t in ps))
+    eps = (ctypes.c_double * max(1, 2 * len(layers)))(
+        *(e for ly in layers for e in (ly.norm1.eps, ly.norm2.eps)))
+    out = torch.empty((B, E), dtype=f, device=dev) if out is None else out
+    call("ocppo_oct_trunk_fwd", _stream(dev), _check(x, "x", f, dev), ptrs, eps, B, S, F, E,
+         num_heads, len(layers), len(post_layers), num_obj, int(bool(masking)),
+         OCT_POOLING[pooling_type], tile_rows, _check(out, "hidden", f, dev, B * E))
+    return out
+
+
 # The feed-forward half of a ViT block, y = x + W2 gelu(W1 LN(x) + b1) + b2, as one launch forward
 # and one (+ finish) backward (csrc/ocppo_vit_ffn.hip, f32 MFMA; DESIGN.md 27.4)
 VIT_FFN_MIN_DIM, VIT_FFN_MAX_DIM, VIT_FFN_DIM_STEP = 32, 128, 32

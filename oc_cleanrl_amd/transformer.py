@@ -16,7 +16,8 @@ runs a block as
 with the four Linears on agents.linear_act (rows = B * S: x6 / hipBLASLt / the rows kernel) and
 the attention core one HIP launch per direction (csrc/ocppo_attn.hip); the residual add +
 LayerNorm has a HIP kernel too (ops.add_layernorm), routed to torch's ops where it measured
-slower (ADD_LAYERNORM_HIP). By default that path needs `dropout == 0`: with the reference's
+slower (ADD_LAYERNORM_HIP). Without an autograd graph (rollout, bootstrap, evaluation) the whole
+trunk is one launch instead (ops.oct_trunk, FUSED_TRUNK). By default both need `dropout == 0`: with the reference's
 default dropout = 0.1 every block runs torch's own layer modules. `--dropout 0` selects the fused
 path; `FUSED_ATTN = False` turns it off (tests, tools/bench_transformer.py).
 
@@ -49,6 +50,12 @@ from .trainer import PPOTrainer, learner_main, run
 
 # The fused block path (ops.mha / ops.add_layernorm); False: torch's layer modules everywhere.
 FUSED_ATTN = True
+
+# Without an autograd graph (the rollout, the bootstrap, evaluation: torch.no_grad()) and at
+# dropout == 0 the whole trunk -- encoder Linear, every block, the post layers, the pooling -- is
+# ONE launch (ops.oct_trunk, csrc/ocppo_oct_trunk.hip) where ops.oct_trunk_ok holds and the measured
+# routing ops.oct_trunk_routed(B, S) sends the size to it. The update is untouched.
+FUSED_TRUNK = True
 
 # The fused path's residual add + LayerNorm on ops.add_layernorm. Off: measured slower than
 # torch's add + layer_norm at both measured shapes (forward + backward, 2560 x 128: 38.4 us against
@@ -239,7 +246,16 @@ class OCTransformerAgent(_ActorCritic):
 
     def trunk(self, x, prescaled: bool = False):
         """The pooled hidden [B, E] (PPOAgent.forward). As the reference, the post layers run only
-        on the masking path."""
+        on the masking path. Under torch.no_grad() at dropout 0: one launch (FUSED_TRUNK)."""
+        if FUSED_TRUNK and not torch.is_grad_enabled() and self.dropout == 0 and \
+                attn_ok(x, self.encoder.out_features, self.num_heads, self.dropout):
+            post = list(self.network)[::2]
+            if ops.oct_trunk_routed(x.shape[0], x.shape[1]) and ops.oct_trunk_ok(
+                    x, self.encoder, self.transformer.layers, post, self.num_heads, self.num_obj,
+                    self.pooling_type):
+                return ops.oct_trunk(x, self.encoder, self.transformer.layers, post,
+                                     self.num_heads, self.masking, self.num_obj,
+                                     self.pooling_type, checked=True)
         if not self.masking:
             h, _ = self.tokens(x, None)
             return pool(h, None, self.pooling_type)

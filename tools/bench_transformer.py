@@ -1,6 +1,6 @@
 """Timings of the transformer block kernels and the transformer trainer.
 
-    python tools/bench_transformer.py [--skip-trainer] [--S 8]
+    python tools/bench_transformer.py [--skip-trainer] [--S 8] [--trunk]
 
 Every case runs twice, alternating in one session after a warm-up, each window bracketed by a
 device synchronise; the yardstick is torch's own path on the same GPU and inputs.
@@ -10,6 +10,10 @@ device synchronise; the yardstick is torch's own path on the same GPU and inputs
            and a scaled one (4096 samples x S = 16)
   trainer  TransformerTrainer env steps/s at --dropout 0, fused path on (with torch's or the HIP
            add + LayerNorm) and off: 128 envs x 128 steps, emb 128, heads 8, blocks 3
+  --trunk  only the inference trunk: agent.trunk under no_grad as a replayed
+           hipGraph, the chain of launches against ops.oct_trunk (the tile rule and each tile size
+           forced), at envs x S = 10 x 8, 128 x 8, 128 x 16 and 4096 x 16; then the trainer's env
+           steps/s with FUSED_TRUNK on and off at the same four sizes
 Prints one JSON line per case and run.
 """
 from __future__ import annotations
@@ -94,10 +98,11 @@ def op_cases(dev, B, S, E=128, heads=8):
             "add_layernorm_hip": hip_ln, "add_layernorm_torch": torch_ln}
 
 
-def trainer_sps(dev, fused: bool, S: int, iters: int = 6, ln_hip: bool = False) -> float:
-    T.FUSED_ATTN, T.ADD_LAYERNORM_HIP = fused, ln_hip
-    args = T.finalize(T.TransformerArgs(num_envs=128, num_steps=128, buffer_window_size=S,
-                                        dropout=0.0, total_timesteps=128 * 128 * 1000,
+def trainer_sps(dev, fused: bool, S: int, iters: int = 6, ln_hip: bool = False,
+                num_envs: int = 128, fused_trunk: bool = True) -> float:
+    T.FUSED_ATTN, T.ADD_LAYERNORM_HIP, T.FUSED_TRUNK = fused, ln_hip, fused_trunk
+    args = T.finalize(T.TransformerArgs(num_envs=num_envs, num_steps=128, buffer_window_size=S,
+                                        dropout=0.0, total_timesteps=num_envs * 128 * 1000,
                                         save_model=False))
     tr = T.TransformerTrainer(args, dev, log=False)
     try:
@@ -111,16 +116,68 @@ def trainer_sps(dev, fused: bool, S: int, iters: int = 6, ln_hip: bool = False) 
         return iters * args.batch_size / (time.perf_counter() - t0)
     finally:
         tr.close()
-        T.FUSED_ATTN, T.ADD_LAYERNORM_HIP = True, False
+        T.FUSED_ATTN, T.ADD_LAYERNORM_HIP, T.FUSED_TRUNK = True, False, True
+
+
+TRUNK_SHAPES = ((10, 8), (128, 8), (128, 16), (4096, 16))
+# more than 16 objects (32- and 64-row workgroups by force): the trunk alone, no trainer runs
+TRUNK_LARGE_S_SHAPES = ((3, 32), (10, 32), (128, 32), (1024, 32), (10, 64), (128, 64), (1024, 64))
+
+
+def trunk_cases(dev, B, S, F=8, E=128, heads=8, blocks=3):
+    """agent.trunk under no_grad: the chain (FUSED_TRUNK off) and the kernel per tile size."""
+    from oc_cleanrl_amd.agents import EnvSpec
+
+    torch.manual_seed(0)
+    ag = T.OCTransformerAgent(EnvSpec((S, F), 6), E, heads, blocks, True, 3, None, dropout=0.0)
+    ag = ag.to(dev)
+    x = torch.randn(B, S, F, device=dev)
+    x[..., :3] = (torch.rand(B, S, 3, device=dev) < 0.4).float()
+    x[:, 0, 0] = 1.0  # every sample has a valid object
+    post = list(ag.network)[::2]
+    out = torch.empty(B, E, device=dev)
+
+    def chain():
+        T.FUSED_TRUNK = False
+        with torch.no_grad():
+            ag.trunk(x)
+        T.FUSED_TRUNK = True
+
+    def kernel(tile):
+        return lambda: ops.oct_trunk(x, ag.encoder, ag.transformer.layers, post, heads, True, 3,
+                                     "max", tile, out)
+
+    cases = {"trunk_chain": chain, f"trunk_kernel_rule{ops.oct_trunk_tile_rows(B, S)}": kernel(0)}
+    cases.update({f"trunk_kernel_{t}": kernel(t) for t in (16, 32, 64) if t >= S})
+    return cases
+
+
+def trunk_main(dev):
+    for B, S in TRUNK_SHAPES + TRUNK_LARGE_S_SHAPES:
+        cases = trunk_cases(dev, B, S)
+        for run in (1, 2):
+            for name, body in cases.items():
+                print(json.dumps({"case": name, "B": B, "S": S, "run": run,
+                                  "us": round(graph_us(body), 2)}), flush=True)
+    for run in (1, 2):
+        for B, S in TRUNK_SHAPES:
+            for on in (True, False):
+                sps = trainer_sps(dev, True, S, iters=3 if B > 1000 else 6, num_envs=B,
+                                  fused_trunk=on)
+                print(json.dumps({"case": "trainer", "fused_trunk": on, "envs": B, "S": S,
+                                  "run": run, "env_steps_per_s": round(sps)}), flush=True)
 
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--S", type=int, default=8, help="objects per observation at the update shape")
     ap.add_argument("--skip-trainer", action="store_true")
+    ap.add_argument("--trunk", action="store_true")
     a = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
+    if a.trunk:
+        return trunk_main(dev)
     for shape, (B, S) in (("update", (320, a.S)), ("scaled", (4096, 16))):
         cases = op_cases(dev, B, S)
         for run in (1, 2):  # alternating: every case once per round
